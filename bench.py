@@ -7,19 +7,24 @@ sweep (gramian YtY + per-row 3-step CG solves) then item half sweep (gramian XtX
 for N > 1 -- the RCCL exchange of the gramians and of the freshly solved factor shards.  Inputs are
 resident in HBM before the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N = 1 workload: BASELINE configs[2] -- last.fm-360K-shaped synthetic CSR (358,868 users x 292,385
 items, ~17.5M nnz requested), factors=128, CG cg_steps=3, fp32.  N > 1: STRONG scaling on BASELINE
 configs[3] (10M users x 1M items x 500M nnz, f=128; the matrix is a fixed 8 x 8 grid of blocks, so
 N = 1, 2, 4, 8 factorise the same matrix; users and items row-sharded over the ranks).  The one-GPU
-point of that curve is `--gpus 1 --shape c4` (the same sharded driver with one rank); the default
-N = 1 line also carries it as the extra `c4_full_1gpu`.  `--weak`: one configs[2]-shaped shard per rank.
+point of that curve is `--gpus 1 --shape c4` (the same sharded driver with one rank); the N = 1
+line with --full also carries it as the extra `c4_full_1gpu`.  `--weak`: one configs[2]-shaped shard per rank.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed on the library
-stream inside the timed region) and `cpu_baseline` (the reference's own Cython CPU solver from
-oracle/_ref, or the plain-C oracle port, on a bounded row sample of the same workload).
+Prints ONE JSON line (rank 0).  A plain N = 1 run sets up, warms up, times the K steps and prints the
+contract keys (`value`, `ms_per_step`, ...) and the workload, nothing else.  `--full` adds everything
+else the benchmark measures: `roofline` (dominant kernel, HIP-event timed on the library stream inside
+the timed region), per-kernel times and clocks from extra passes, top-k, `cpu_baseline` (the
+reference's own Cython CPU solver from oracle/_ref, or the plain-C oracle port, on a bounded row sample
+of the same workload), the secondary configurations and the detail side file.  `--dump-outputs DIR`
+(N = 1): the user and item factors as the last timed step left them, DIR/{user,item}_factors.npy.
+The sharded driver (N > 1, `--shape c4`) prints the same record with or without --full.
 """
 import argparse
 import json
@@ -58,7 +63,31 @@ def parse_args():
     ap.add_argument("--weak", action="store_true",
                     help="--gpus N > 1: weak scaling on one configs[2]-shaped shard per GPU instead of strong scaling on configs[3]")
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary objects (cholesky_c2, cg_c5, ...)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline and per-kernel times, clocks, top-k, CPU "
+                         "baselines, secondary configurations, the detail side file (off: set up, warm up, time, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the factors the last step computed to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES_PER_MATRIX = 16 << 20  # --dump-outputs: at most 16 MB per factor matrix, 32 MB in all
+
+
+def dump_outputs(path, named):
+    """Writes what a caller of the timed path receives (`named`: name -> gpu.Matrix) as DIR/<name>.npy, float32.  A matrix
+    larger than DUMP_BYTES_PER_MATRIX is written as a fixed, seeded sample of its rows (sorted row ids, the same for every
+    run of the same shape), so two builds can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    for name, M in named.items():
+        A = M.to_numpy()
+        rows = DUMP_BYTES_PER_MATRIX // (4 * max(1, A.shape[1]))
+        if A.shape[0] > rows:
+            A = A[np.sort(np.random.default_rng(0).choice(A.shape[0], rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(A, dtype=np.float32))
 
 
 def cg_algorithmic_bytes(lengths, f):
@@ -248,6 +277,8 @@ def main():
     # N > 1, or the one-GPU point of the configs[3] strong-scaling curve (`--gpus 1 --shape c4`); the env knob exercises
     # the N > 1 code path (chunked, pipelined exchange) with one rank
     if world > 1 or args.shape == "c4" or os.environ.get("IMP_FORCE_SHARDED"):
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs is implemented for the single-GPU workload only")
         from implicit_amd.gpu import sharded
 
         def rank0_roofline(Cui, Ciu, timed, steps):
@@ -310,27 +341,36 @@ def main():
         if deferred:
             gpu.synchronize()
 
-    clock_idle = round(gpu.core_clock_mhz(50), 1)
+    clock_idle = round(gpu.core_clock_mhz(50), 1) if args.full else None
     gpu.set_deferred_sync(deferred)
     for _ in range(args.warmup):
         step()
     gpu.synchronize()
     # HIP-event pairs cost stream time (~0.2 ms per iteration for all ~30 launches), so the timed region carries them
     # only for the dominant kernel family -- the mid-row team kernels of the CG sweep -- which is what `roofline`
-    # reports; the per-kernel breakdown comes from a separate, untimed pass below.
+    # reports; the per-kernel breakdown comes from a separate, untimed pass below.  A plain run (no --full) carries none.
     timed_filter = "als_cg_half_sweep" if args.solver == "cg" else None
-    gpu.Profiler.reset()
-    gpu.Profiler.enable(os.environ.get("IMP_BENCH_NO_PROF") is None, only=timed_filter)
+    if args.full:
+        gpu.Profiler.reset()
+        gpu.Profiler.enable(os.environ.get("IMP_BENCH_NO_PROF") is None, only=timed_filter)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     gpu.synchronize()
     elapsed = time.perf_counter() - t0
-    gpu.Profiler.enable(False)
-    timed = {name: gpu.Profiler.get(name) for name in gpu.Profiler.names()}
+    timed = {}
+    if args.full:
+        gpu.Profiler.enable(False)
+        timed = {name: gpu.Profiler.get(name) for name in gpu.Profiler.names()}
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = (users + items) / (elapsed / args.steps)
+    if args.dump_outputs:  # before anything else runs a step: X and Y as the last timed step left them
+        dump_outputs(args.dump_outputs, {"user_factors": X, "item_factors": Y})
+    if not args.full:
+        gpu.set_deferred_sync(False)
+        emit(saved_stdout, plain_line(headline_record(args, users, items, Cui, value, ms_per_step)))
+        return
 
     detail_steps = min(args.steps, 3)
     gpu.Profiler.reset()
@@ -402,26 +442,8 @@ def main():
                           "achieved_GBps": total_bytes / (elapsed / args.steps) / 1e9,
                           "frac_of_8TBps": total_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS}
 
-    out = {
-        "metric": "ALS user+item updates/sec per iteration (factors=128); top-k recs/sec",
-        "value": value,
-        "unit": "updates/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": f"BASELINE configs[2]: last.fm-360K-shaped synthetic CSR, ALS CG cg_steps={CG_STEPS}"
-                        if (args.shape, args.scale, args.solver, FACTORS) == ("lastfm360k", 1.0, "cg", 128)
-                        else f"{args.shape} x{args.scale} f={FACTORS} {args.solver} (not the headline configuration)",
-            "users": users, "items": items, "nnz": int(Cui.nnz), "factors": FACTORS, "regularization": REG,
-            "solver": args.solver, "cg_steps": CG_STEPS if args.solver == "cg" else None, "parallelism": "1 GPU",
-        },
+    out = headline_record(args, users, items, Cui, value, ms_per_step)
+    out.update({
         "nnz_visits_per_s": 2 * int(Cui.nnz) / (elapsed / args.steps),
         "roofline": roofline,
         "iteration_roofline": iteration_roofline,
@@ -432,7 +454,7 @@ def main():
         "core_clock_mhz": {"behind_a_step": clock_mhz, "beside_queued_steps": clock_beside, "before_warmup": clock_idle,
                            "note": "imp_debug_core_clock: core cycles over 50 us of the constant-rate wall clock, one wavefront "
                                    "queued behind the work named"},
-    }
+    })
 
     if not args.no_topk:
         out["topk"] = bench_topk(gpu, Cui, X, Y, k=10)
@@ -459,6 +481,41 @@ def main():
                 out[name + "_error"] = f"{type(e).__name__}: {e}"
             out.setdefault("extras_s", {})[name] = round(time.time() - t0, 1)
     emit(saved_stdout, compact_line(out, args))
+
+
+def headline_record(args, users, items, Cui, value, ms_per_step):
+    """The contract keys and the workload of the single-GPU line: all a plain run (no --full) measures and prints."""
+    return {
+        "metric": "ALS user+item updates/sec per iteration (factors=128); top-k recs/sec",
+        "value": value,
+        "unit": "updates/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"BASELINE configs[2]: last.fm-360K-shaped synthetic CSR, ALS CG cg_steps={CG_STEPS}"
+                        if (args.shape, args.scale, args.solver, FACTORS) == ("lastfm360k", 1.0, "cg", 128)
+                        else f"{args.shape} x{args.scale} f={FACTORS} {args.solver} (not the headline configuration)",
+            "users": users, "items": items, "nnz": int(Cui.nnz), "factors": FACTORS, "regularization": REG,
+            "solver": args.solver, "cg_steps": CG_STEPS if args.solver == "cg" else None, "parallelism": "1 GPU",
+        },
+    }
+
+
+def plain_line(h):
+    """The line of a plain run: the contract keys and the workload, rounded as in compact_line; no side file."""
+    line = {k: h[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                              "scaling", "vs_baseline", "dtype", "data")}
+    line["value"], line["ms_per_step"] = _r(line["value"]), _r(line["ms_per_step"], 4)
+    c = h["config"]
+    line["config"] = {k: c[k] for k in ("workload", "users", "items", "nnz", "factors", "solver", "cg_steps")}
+    return line
 
 
 def compact_line(full, args):

@@ -4,7 +4,7 @@
 set -u
 TAG=${1:-pmcab}; R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-topk --no-extras"
+B="python $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-topk --no-extras"
 for arm in old new; do
   if [ $arm = old ]; then export IMP_TEAM_FUSED=0; else unset IMP_TEAM_FUSED; fi
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/${arm}_stats -- $B > $O/${arm}_bench.json 2> $O/${arm}_stats.err
