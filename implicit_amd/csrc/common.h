@@ -178,6 +178,7 @@ struct Context {
   DeviceArray<float> w256_ws;                    // fp16-split gramian in fragment order + header (als_cg_w256.hip)
   DeviceArray<unsigned> nm_fix_rows;             // rows the normal-matrix kernels left to the fix-up kernel (operands beyond the fp16 range)
   DeviceArray<int> nm_ticket;                    // work counter of the normal-matrix kernel (als_cg_nm.hip), reset by every launch
+  DeviceArray<unsigned long long> bpr_stats;     // correct / skipped counts and the id check's violation bits of bpr_update (bpr.hip)
 };
 inline hipStream_t stream() { return ctx().stream; }
 // a C-ABI entry point is about to write `bytes` at `dst` through the library (or the memory is being freed): a padded copy of Y

@@ -6,25 +6,9 @@
 // nor the CPU path's numpy Generator is reproduced (no reference test depends on specific random
 // values); parity runs inject identical initial factors from the host instead.
 #include "common.h"
+#include "philox.h"
 
 namespace imp {
-
-struct u32x4 {
-  uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-    uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-    uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0, c1 = n1, c2 = n2, c3 = n3;
-    k0 += W0, k1 += W1;
-  }
-  return {c0, c1, c2, c3};
-}
 
 __device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }  // (0,1)
 

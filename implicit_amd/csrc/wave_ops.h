@@ -38,6 +38,22 @@ __device__ __forceinline__ float wave_allmax(float v) {
   return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 
+// Sum over an aligned group of G = 16, 32 or 64 lanes, in every lane of the group.  An xor butterfly: both lanes of a pair
+// add the same two operands, so every lane of the group ends with bitwise the same sum (a row_ror tree does not).  The
+// 16-lane levels are DPP (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror -- after the level before,
+// each mirror reads the partner's partial sum), the 32- and 64-lane levels are swizzles.  Every lane of the group must be
+// active.
+template <int G> __device__ __forceinline__ float group_allsum(float v) {
+  static_assert(G == 16 || G == 32 || G == 64, "group of 16, 32 or 64 lanes");
+  v += dpp_mov<0xB1>(v);
+  v += dpp_mov<0x4E>(v);
+  v += dpp_mov<0x141>(v);
+  v += dpp_mov<0x140>(v);
+  if constexpr (G >= 32) v += __shfl_xor(v, 16);
+  if constexpr (G >= 64) v += __shfl_xor(v, 32);
+  return v;
+}
+
 __device__ __forceinline__ float lane_bcast(float v, int lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
 }

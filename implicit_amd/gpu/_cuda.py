@@ -378,8 +378,26 @@ def get_device_count():
 
 
 def bpr_update(*args, **kwargs):
-    """_cuda.pyx:288-297.  BPR is outside this build's hot path."""
+    """_cuda.pyx:288-297.  Kept raising NotImplementedError (pinned by the tests); BPR training is bpr_epoch."""
     raise NotImplementedError("bpr_update is not part of the MI355X ALS hot path")
+
+
+def bpr_epoch(userids, itemids, indptr, X, Y, learning_rate, regularization, seed, verify_negative, samples=None):
+    """One SGD pass of Bayesian Personalized Ranking (imp_bpr_update, bpr.hip): the first nine arguments are those of the
+    reference's bpr_update (_cuda.pyx:288-297), returns (correct, skipped).  `samples`: the number of sampled triples, None
+    for one epoch (nnz).  X / Y are updated in place.  Numerics are the reference's CPU update (cpu/bpr.pyx:249-302); the
+    sample pairs are a Philox stream of (seed, sample index, nnz), so `skipped` is reproducible.  An id outside its matrix
+    raises IndexError before anything is written.  Named apart from bpr_update, which keeps its NotImplementedError."""
+    for name, v in (("userids", userids), ("itemids", itemids), ("indptr", indptr)):
+        if not isinstance(v, IntVector):
+            raise TypeError(f"bpr_epoch: {name} must be an implicit_amd.gpu.IntVector")
+    if not isinstance(X, Matrix) or not isinstance(Y, Matrix):
+        raise TypeError("bpr_epoch: X and Y must be implicit_amd.gpu.Matrix objects")
+    correct, skipped = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().imp_bpr_update(userids._h, itemids._h, indptr._h, X._h, Y._h, float(learning_rate), float(regularization),
+                               int(seed), 1 if verify_negative else 0, -1 if samples is None else int(samples),
+                               ctypes.byref(correct), ctypes.byref(skipped)))
+    return correct.value, skipped.value
 
 
 class Comm:

@@ -82,6 +82,9 @@ _SIGNATURES = {
                            c_void_pp],
     "imp_random_randn": [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_float, ctypes.c_float,
                          c_void_pp],
+    "imp_bpr_update": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                       ctypes.c_float, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                       ctypes.POINTER(ctypes.c_int64)],
     "imp_comm_unique_id": [ctypes.c_void_p],
     "imp_comm_init_rank": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_void_pp],
     "imp_comm_destroy": [ctypes.c_void_p],

@@ -190,6 +190,21 @@ int imp_random_destroy(imp_random *r);
 int imp_random_uniform(imp_random *r, size_t rows, size_t cols, float low, float high, imp_matrix **out);
 int imp_random_randn(imp_random *r, size_t rows, size_t cols, float mean, float stddev, imp_matrix **out);
 
+/* ---- BPR training (bpr.h:8-13, bpr.cu:72-125) ------------------------------------------------------ */
+/* One SGD pass of Bayesian Personalized Ranking over `samples` sampled (user, liked, disliked) triples (samples < 0: nnz, one
+ * epoch).  userids / itemids: the COO row / column ids of the training matrix (nnz each); indptr: its CSR row pointer
+ * (X.rows + 1 entries; row indices sorted when verify_negative is set).  X (users x C), Y (items x C), fp32, C = factors + 1
+ * in 2 .. 1024, column C-1 the item bias (users hold 1.0 there; X[:, C-1] is never written).  The update is the reference's
+ * CPU one (implicit/cpu/bpr.pyx:249-302), the sample pairs a counter-based Philox stream of (seed, sample index, nnz):
+ * bpr.hip states both.  *correct: samples with z < 0.5; *skipped: samples whose negative the user had liked.  Synchronous,
+ * deferred mode included.  Every id is checked on the device before the update runs: IMP_OUT_OF_RANGE (IndexError), with
+ * X and Y untouched, for a user id outside X, an item id outside Y or an indptr entry outside [0, nnz].
+ * IMP_INVALID_ARGUMENT: column counts differ or outside 2 .. 1024, a matrix not fp32, userids / itemids of different sizes,
+ * indptr not X.rows + 1 long.  nnz = 0 returns (0, 0) without a launch. */
+int imp_bpr_update(const imp_intvector *userids, const imp_intvector *itemids, const imp_intvector *indptr, imp_matrix *X,
+                   imp_matrix *Y, float learning_rate, float regularization, int64_t seed, int verify_negative, int64_t samples,
+                   int64_t *correct, int64_t *skipped);
+
 /* ---- NEW: multi-GPU exchange over RCCL / xGMI (no reference counterpart) ------------------------ */
 /* One process per GPU.  Rank 0 calls imp_comm_unique_id, the host side broadcasts the 128 bytes by
  * any means (torch.distributed store, MPI, a file) and every rank calls imp_comm_init_rank. */
