@@ -179,6 +179,7 @@ struct Context {
   DeviceArray<unsigned> nm_fix_rows;             // rows the normal-matrix kernels left to the fix-up kernel (operands beyond the fp16 range)
   DeviceArray<int> nm_ticket;                    // work counter of the normal-matrix kernel (als_cg_nm.hip), reset by every launch
   DeviceArray<unsigned long long> bpr_stats;     // correct / skipped counts and the id check's violation bits of bpr_update (bpr.hip)
+  DeviceArray<float> lmf_ws;                     // partial sums of the long rows' segments of lmf_update (lmf.hip)
 };
 inline hipStream_t stream() { return ctx().stream; }
 // a C-ABI entry point is about to write `bytes` at `dst` through the library (or the memory is being freed): a padded copy of Y

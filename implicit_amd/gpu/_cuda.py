@@ -7,7 +7,8 @@ bpr_update.  Host code stays Python; every heavy call goes through the C-ABI wit
 released (ctypes.CDLL does that), as the reference does with `with nogil` (_cuda.pyx:79,257,264,271).
 
 NEW relative to the reference: LeastSquaresSolver.least_squares_cholesky (the reference GPU path
-has no Cholesky solver) and the Comm class (RCCL exchange for the multi-GPU fit).
+has no Cholesky solver), the Comm class (RCCL exchange for the multi-GPU fit) and lmf_update (the
+reference has no GPU LMF).
 """
 import ctypes
 
@@ -398,6 +399,25 @@ def bpr_epoch(userids, itemids, indptr, X, Y, learning_rate, regularization, see
                                int(seed), 1 if verify_negative else 0, -1 if samples is None else int(samples),
                                ctypes.byref(correct), ctypes.byref(skipped)))
     return correct.value, skipped.value
+
+
+def lmf_update(cui, X, Y, deriv_sum_sq, learning_rate, regularization, neg_prop, seed, one_col=-1):
+    """One Adagrad half-sweep of Logistic Matrix Factorization (imp_lmf_update, lmf.hip): X is updated in place against
+    the read-only Y over the CSRMatrix `cui` (rows of X x rows of Y, values = confidences), deriv_sum_sq (the shape of X)
+    accumulates the squared gradients.  Numerics are the reference's CPU update (cpu/lmf.pyx lmf_update), with at most
+    C = X.shape[1] negatives per row as there; the negatives are a Philox stream of (seed, row, k), so the result is
+    deterministic.  Afterwards column `one_col` of X is 1.0 in every row (-1: none).  Bad shapes, dtypes or arguments
+    raise ValueError with X and deriv_sum_sq untouched."""
+    if not isinstance(cui, CSRMatrix):
+        raise TypeError("lmf_update: cui must be an implicit_amd.gpu.CSRMatrix")
+    for name, v in (("X", X), ("Y", Y), ("deriv_sum_sq", deriv_sum_sq)):
+        if not isinstance(v, Matrix):
+            raise TypeError(f"lmf_update: {name} must be an implicit_amd.gpu.Matrix")
+    neg_prop, one_col = int(neg_prop), int(one_col)
+    if not (0 <= neg_prop < 2**31 and -1 <= one_col < 2**31):
+        raise ValueError("lmf_update: neg_prop must lie in [0, 2^31) and one_col in [-1, C)")
+    check(lib().imp_lmf_update(cui._h, X._h, Y._h, deriv_sum_sq._h, float(learning_rate), float(regularization), neg_prop,
+                               int(seed), one_col))
 
 
 class Comm:

@@ -85,6 +85,8 @@ _SIGNATURES = {
     "imp_bpr_update": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
                        ctypes.c_float, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                        ctypes.POINTER(ctypes.c_int64)],
+    "imp_lmf_update": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
+                       ctypes.c_int, ctypes.c_int64, ctypes.c_int],
     "imp_comm_unique_id": [ctypes.c_void_p],
     "imp_comm_init_rank": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_void_pp],
     "imp_comm_destroy": [ctypes.c_void_p],

@@ -205,6 +205,19 @@ int imp_bpr_update(const imp_intvector *userids, const imp_intvector *itemids, c
                    imp_matrix *Y, float learning_rate, float regularization, int64_t seed, int verify_negative, int64_t samples,
                    int64_t *correct, int64_t *skipped);
 
+/* ---- LMF training (no reference GPU counterpart: implicit/lmf.py raises for use_gpu=True) --------------------------- */
+/* One Adagrad half-sweep of Logistic Matrix Factorization: X (rows of cui x C) is updated against the read-only Y (columns
+ * of cui x C), deriv_sum_sq (shape of X) accumulates the squared gradients.  fp32, C = factors + 2 in 3 .. 1024.  The
+ * update is the reference's CPU one (implicit/cpu/lmf.pyx lmf_update), including its cap of K = min(C, n * neg_prop)
+ * negatives per row of n nonzeros; the negatives are a counter-based Philox stream of (seed, row, k): lmf.hip states both.
+ * Rows without a nonzero are not touched; afterwards column one_col of X is 1.0 in every row (-1: no column).  The result
+ * is deterministic (bitwise equal for equal inputs).  Synchronous, deferred mode included.  nnz = 0 only sets one_col.
+ * IMP_INVALID_ARGUMENT, with X and deriv_sum_sq untouched: X.rows != cui rows, Y.rows != cui columns, column counts or
+ * deriv_sum_sq's shape disagree, a matrix not fp32, C outside 3 .. 1024, neg_prop < 0, one_col outside [-1, C), X, Y and
+ * deriv_sum_sq sharing storage, or a CSR held in several blocks (more than 2^31 - 1 nonzeros; not supported). */
+int imp_lmf_update(const imp_csr *cui, imp_matrix *X, const imp_matrix *Y, imp_matrix *deriv_sum_sq, float learning_rate,
+                   float regularization, int neg_prop, int64_t seed, int one_col);
+
 /* ---- NEW: multi-GPU exchange over RCCL / xGMI (no reference counterpart) ------------------------ */
 /* One process per GPU.  Rank 0 calls imp_comm_unique_id, the host side broadcasts the 128 bytes by
  * any means (torch.distributed store, MPI, a file) and every rank calls imp_comm_init_rank. */
