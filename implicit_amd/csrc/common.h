@@ -180,6 +180,9 @@ struct Context {
   DeviceArray<int> nm_ticket;                    // work counter of the normal-matrix kernel (als_cg_nm.hip), reset by every launch
   DeviceArray<unsigned long long> bpr_stats;     // correct / skipped counts and the id check's violation bits of bpr_update (bpr.hip)
   DeviceArray<float> lmf_ws;                     // partial sums of the long rows' segments of lmf_update (lmf.hip)
+  DeviceArray<double> knn_acc;                   // dense per-worker accumulators of sparse_topk_product, kept at a sentinel (knn.hip)
+  DeviceArray<int32_t> knn_touched;              // the workers' touched-column lists (knn.hip)
+  int knn_cols = -1;                             // column count knn_acc is laid out for
 };
 inline hipStream_t stream() { return ctx().stream; }
 // a C-ABI entry point is about to write `bytes` at `dst` through the library (or the memory is being freed): a padded copy of Y

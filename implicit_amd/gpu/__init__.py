@@ -11,8 +11,8 @@ HAS_RMM = False
 
 try:
     from ._cuda import (COOMatrix, Comm, CSRMatrix, IntVector, KnnQuery, LeastSquaresSolver, Matrix,  # noqa: F401
-                        Profiler, RandomState, bpr_epoch, bpr_update, calculate_norms, core_clock_mhz, debug_occupy, fixup_rows, get_device, get_device_count, get_oversubscribe, lmf_update, release_workspaces,
-                        set_deferred_sync, set_device, set_oversubscribe, synchronize)
+                        Profiler, RandomState, SpMat, bpr_epoch, bpr_update, calculate_norms, core_clock_mhz, debug_occupy, fixup_rows, get_device, get_device_count, get_oversubscribe, lmf_update, release_workspaces,
+                        set_deferred_sync, set_device, set_oversubscribe, sparse_topk_product, synchronize)
     from ._hip import lib as _lib
 
     _lib()  # ImportError when libimplicit_hip.so has not been built

@@ -7,8 +7,8 @@ bpr_update.  Host code stays Python; every heavy call goes through the C-ABI wit
 released (ctypes.CDLL does that), as the reference does with `with nogil` (_cuda.pyx:79,257,264,271).
 
 NEW relative to the reference: LeastSquaresSolver.least_squares_cholesky (the reference GPU path
-has no Cholesky solver), the Comm class (RCCL exchange for the multi-GPU fit) and lmf_update (the
-reference has no GPU LMF).
+has no Cholesky solver), the Comm class (RCCL exchange for the multi-GPU fit), lmf_update (the
+reference has no GPU LMF) and SpMat / sparse_topk_product (the reference's nearest-neighbour models are CPU only).
 """
 import ctypes
 
@@ -418,6 +418,54 @@ def lmf_update(cui, X, Y, deriv_sum_sq, learning_rate, regularization, neg_prop,
         raise ValueError("lmf_update: neg_prop must lie in [0, 2^31) and one_col in [-1, C)")
     check(lib().imp_lmf_update(cui._h, X._h, Y._h, deriv_sum_sq._h, float(learning_rate), float(regularization), neg_prop,
                                int(seed), one_col))
+
+
+class SpMat:
+    """NEW: an fp64-valued CSR on the device (imp_spmat), an operand of sparse_topk_product.  Any scipy sparse matrix is
+    taken as CSR (converted without a warning); values become float64, offsets int64, column ids int32.  The stored order
+    of every row's entries is kept: it is the summation order of the product."""
+
+    def __init__(self, X):
+        import scipy.sparse
+
+        X = X if isinstance(X, scipy.sparse.csr_matrix) else scipy.sparse.csr_matrix(X)
+        indptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
+        indices = np.asarray(X.indices)
+        if indices.dtype != np.int32:
+            if len(indices) and (indices.max() > np.iinfo(np.int32).max or indices.min() < 0):
+                raise ValueError("column index out of range for SpMat")
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(X.data, dtype=np.float64)
+        self.shape = (int(X.shape[0]), int(X.shape[1]))
+        if max(self.shape) > np.iinfo(np.int32).max:
+            raise ValueError("SpMat: dimensions must fit int32")
+        self.nnz = len(data)
+        self._h = ctypes.c_void_p()
+        check(lib().imp_spmat_create(self.shape[0], self.shape[1], self.nnz, _vp(indptr), _vp(indices), _vp(data),
+                                     ctypes.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().imp_spmat_destroy(self._h)
+            self._h = None
+
+
+def sparse_topk_product(A, B, k, zero_own_columns=False):
+    """NEW: row r of A.B over its touched columns, the k best under (score, id) descending (imp_sparse_topk_product,
+    knn.hip).  A and B are SpMat handles; returns (ids int32, scores float64, counts int32) with ids / scores of shape
+    (A.rows, k), counts[r] = min(k, touched columns of row r), entries past counts[r] = (-1, -inf).  zero_own_columns sets
+    every touched column of A[r] to 0.0 (it stays a candidate).  Argument errors raise ValueError."""
+    if not isinstance(A, SpMat) or not isinstance(B, SpMat):
+        raise TypeError("sparse_topk_product: A and B must be implicit_amd.gpu.SpMat")
+    k = int(k)
+    if not 1 <= k < 2**31:
+        raise ValueError("sparse_topk_product: k must be >= 1")
+    rows = A.shape[0]
+    ids = np.empty((rows, k), dtype=np.int32)
+    scores = np.empty((rows, k), dtype=np.float64)
+    counts = np.empty(rows, dtype=np.int32)
+    check(lib().imp_sparse_topk_product(A._h, B._h, k, 1 if zero_own_columns else 0, _vp(ids), _vp(scores), _vp(counts)))
+    return ids, scores, counts
 
 
 class Comm:

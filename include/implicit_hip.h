@@ -218,6 +218,23 @@ int imp_bpr_update(const imp_intvector *userids, const imp_intvector *itemids, c
 int imp_lmf_update(const imp_csr *cui, imp_matrix *X, const imp_matrix *Y, imp_matrix *deriv_sum_sq, float learning_rate,
                    float regularization, int neg_prop, int64_t seed, int one_col);
 
+/* ---- item-item nearest neighbours (reference: the CPU all_pairs_knn / NearestNeighboursScorer, _nearest_neighbours.pyx) -- */
+typedef struct imp_spmat imp_spmat; /* fp64-valued CSR, device-resident: int64 offsets, int32 column ids */
+/* Copies a host CSR to the device.  IMP_INVALID_ARGUMENT: negative sizes, more than 2^31 - 1 nonzeros, indptr not running
+ * from 0 to nnz or decreasing, a column id outside [0, cols). */
+int imp_spmat_create(int32_t rows, int32_t cols, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                     const double *data, imp_spmat **out);
+int imp_spmat_destroy(imp_spmat *m);
+/* Row r of A.B over its TOUCHED columns (reached by at least one pair A[r,u] B[u,j], a 0.0 sum included), fp64, each
+ * column's sum in A[r]'s stored order as the reference's SparseMatrixMultiplier takes it (knn.hip states the contract).
+ * zero_own_columns: every touched column that is also a column of A[r] gets 0.0 and stays a candidate (remove_own_likes).
+ * ids / scores: rows(A) x k on the host, each row the k best under (score, id) descending; counts[r] = min(k, touched);
+ * entries past counts[r] hold id -1 and score -inf.  Deterministic; exact for any k.  Synchronous.
+ * IMP_INVALID_ARGUMENT, nothing written: A.cols != B.rows, k < 1, more than 2^31 - 1 nonzeros, zero_own_columns with
+ * A.cols != B.cols, or a column repeated within a row of B. */
+int imp_sparse_topk_product(const imp_spmat *A, const imp_spmat *B, int k, int zero_own_columns, int32_t *ids,
+                            double *scores, int32_t *counts);
+
 /* ---- NEW: multi-GPU exchange over RCCL / xGMI (no reference counterpart) ------------------------ */
 /* One process per GPU.  Rank 0 calls imp_comm_unique_id, the host side broadcasts the 128 bytes by
  * any means (torch.distributed store, MPI, a file) and every rank calls imp_comm_init_rank. */
