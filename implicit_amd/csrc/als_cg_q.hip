@@ -3,9 +3,11 @@
 // Arithmetic contract: the oracle's CG (implicit/cpu/_als.pyx:152-248).  Kernels -- all on quarter-layout register tiles
 // (als_qtile.h), the whole row resident for all 1 + cg_steps passes:
 //   short rows (<= 32 nnz)   f = 128: one wavefront per row, 16 rows per workgroup in lock step, the gramian product on the bf16
-//                            matrix cores (als_cg_qf.hip als_cg_qfgroup_kernel);  f = 64: independent wavefronts (team width 1)
-//   mid rows (33 .. 512)     a team of 2 / 4 / 8 / 16 wavefronts per row, leader protocol (als_cg_qf.hip als_cg_qfteam_kernel);
-//                            float16 storage: packed 64-entry tiles, half the wavefronts per row (als_cg_qh.hip)
+//                            matrix cores (als_cg_qf.hip als_cg_qfgroup_kernel);  f = 64: independent wavefronts (team width 1,
+//                            als_cg_qfteam_kernel, both storages)
+//   mid rows (33 .. 512)     a team of wavefronts per row, leader protocol (team_rows, als_qf_common.h): fp32 storage on
+//                            32-entry fp32 tiles, 2 / 4 / 8 / 16 wavefronts (als_cg_qf.hip als_cg_qfteam_kernel); float16
+//                            storage on 64-entry tiles of packed halves, half the wavefronts (als_cg_qh.hip als_cg_q64team_kernel)
 // (The first generation of these kernels -- every wavefront of a team repeating the CG arithmetic, rounds 1-2 -- and the
 // IMP_TEAM_FUSED / IMP_SHORT_TEAM1 / IMP_TILE64 switches that selected them were removed in round 6.)
 #include <type_traits>
@@ -15,7 +17,7 @@
 
 namespace imp {
 
-// als_cg_qf.hip
+// als_cg_qf.hip (float16 storage: only the f = 64 short rows go to launch_team_fused)
 template <typename T>
 void launch_team_fused(const imp_csr *C, int f, int width, int first, int count, T *X, const T *Y, const float *A0, int cg_steps,
                        const char *name);

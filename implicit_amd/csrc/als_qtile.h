@@ -11,7 +11,7 @@
 //   * the accumulator (FE factors per lane, partial over the group's entries) is brought back to the COMPACT
 //     layout -- lane (g, m) owns FC = f/64 of its FE expanded slots, slots FC g + c -- by a two-level reduce-scatter across the
 //     groups (FE/2 v_permlane32_swap + FE/4 v_permlane16_swap);  the CG state x, r, p, Ap lives in compact form and
-//     only the operand vector of a pass is expanded to FE per lane (3 FC swaps).
+//     only the operand vector of a pass is expanded to FE per lane (read back from a natural-order copy in memory).
 // About 150 VALU instructions per full-tile pass instead of ~330, and entries beyond the row's count are skipped
 // in whole steps (4 q >= cnt is wave-uniform).
 #ifndef IMPLICIT_AMD_CSRC_ALS_QTILE_H_
@@ -71,28 +71,6 @@ template <int F, typename T> __device__ __forceinline__ void store_compact(T *__
   }
 }
 
-// all-gather across the 4 groups: compact (FC per lane) -> expanded (FE per lane)
-template <int F> __device__ __forceinline__ void expand_vector(const float (&vc)[F / 64], float (&ve)[F / 16]) {
-  constexpr int FC = QL<F>::FC;
-  float pair[2 * FC];  // values of the even / odd group of this lane's group pair
-#pragma unroll
-  for (int c = 0; c < FC; ++c) {
-    float a = vc[c], b = vc[c];
-    // odd rows of a <-> even rows of b: afterwards a = the even group's value, b = the odd group's, in both rows
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    pair[c] = a;
-    pair[FC + c] = b;
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * FC; ++i) {
-    float a = pair[i], b = pair[i];
-    // lanes 32-63 of a <-> lanes 0-31 of b: a = the value held by groups 0/1, b = the value held by groups 2/3
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    ve[i] = a;
-    ve[2 * FC + i] = b;
-  }
-}
-
 // reduce-scatter across the 4 groups: expanded partial sums (FE per lane) -> compact totals (FC per lane)
 template <int F> __device__ __forceinline__ void reduce_expanded(const float (&ae)[F / 16], float (&ac)[F / 64]) {
   constexpr int FE = QL<F>::FE, FC = QL<F>::FC;
@@ -109,53 +87,7 @@ template <int F> struct QTile {
   int cnt;                        // valid entries of the whole 32-entry tile (wave-uniform)
 };
 
-// entry t = 4 q + g of the tile covers nnz k0 + t; lanes past the end repeat the last valid entry with weight 0
-template <int F, typename T>
-__device__ __forceinline__ void load_qtile(QTile<F> &tile, const int32_t *__restrict__ indices,
-                                           const float *__restrict__ data, const T *__restrict__ Y, int lane, int k0,
-                                           int end) {
-  constexpr int FE = QL<F>::FE, EQ = QL<F>::EQ;
-  const int cnt = max(0, min(4 * EQ, end - k0));
-  tile.cnt = cnt;
-  const int g = lane >> 4;
-  unsigned col[EQ];
-#pragma unroll
-  for (int q = 0; q < EQ; ++q) {
-    const int t = 4 * q + g;
-    const bool ok = t < cnt;
-    const int k = k0 + (cnt > 0 ? min(t, cnt - 1) : 0);
-    col[q] = cnt > 0 ? (unsigned)indices[k] : 0u;
-    tile.c[q] = ok ? data[k] : -1.f;
-  }
-  // gathers back to back, in two wave-uniform halves (q < 4 covers tile entries 0..15); few branches keep the
-  // compiler's vmcnt bookkeeping exact so that all loads of a half are in flight together
-  auto gather = [&](int q) {
-    const T *src = Y + (size_t)col[q] * F + 4 * (lane & 15);
-#pragma unroll
-    for (int e = 0; e < FE; e += 4) {
-      const float4 v = load4(src + 16 * e);  // expanded slots e..e+3 = factors 64 (e/4) + 4 m ..
-      tile.y[q][e] = v.x, tile.y[q][e + 1] = v.y, tile.y[q][e + 2] = v.z, tile.y[q][e + 3] = v.w;
-    }
-  };
-  auto clear = [&](int q) {
-#pragma unroll
-    for (int e = 0; e < FE; ++e) tile.y[q][e] = 0.f;
-  };
-  if (cnt > 16) {
-#pragma unroll
-    for (int q = 0; q < EQ; ++q) gather(q);
-  } else if (cnt > 0) {
-#pragma unroll
-    for (int q = 0; q < EQ / 2; ++q) gather(q);
-#pragma unroll
-    for (int q = EQ / 2; q < EQ; ++q) clear(q);
-  } else {
-#pragma unroll
-    for (int q = 0; q < EQ; ++q) clear(q);
-  }
-}
-
-// Staged variant for the resident kernels: the (column, confidence) pairs of a tile are fetched one row AHEAD, one entry
+// Staged entries for the resident kernels: the (column, confidence) pairs of a tile are fetched one row AHEAD, one entry
 // per lane (lanes l and l + 32 both hold entry min(l, cnt - 1) of the slice) -- two registers that stay in flight
 // during the previous row's CG passes -- so that a row starts with its gather addresses already in hand (one HBM
 // round trip per row on the critical path instead of two).  `end` > 0 and [end - 1] must be a valid entry.
@@ -263,42 +195,6 @@ __device__ __forceinline__ void qtile_apply(const QTile<F> &tile, const float (&
       axpy(q, d0);
       axpy(q + 1, d1);
     }
-  }
-}
-
-// Dense part split over the groups: group g adds A0[j][.] * v[j] for j = j_begin + 4 s + g, s = 0..NJ-1.  `vec_lds` is
-// this wave's private LDS copy of the operand vector in natural factor order (wave-synchronous: written by the caller,
-// no barrier).  With a tile resident the compiler is at its register limit and would issue the LDS reads one at a
-// time, each waiting out the full LDS latency; the loop is therefore staged by hand -- the reads of B steps are issued
-// back to back into their own registers, then consumed.
-template <int F, int NJ>
-__device__ __forceinline__ void gram_matvec_q(const float *A0s, int lda, const float *vec_lds, int lane, int j_begin,
-                                              float (&ae)[F / 16]) {
-  constexpr int FE = QL<F>::FE, B = NJ % 4 == 0 ? 4 : (NJ % 2 == 0 ? 2 : 1);
-  const int g = lane >> 4;
-  const float *vp = vec_lds + j_begin + g;
-  const float *row = A0s + (size_t)(j_begin + g) * lda + 4 * (lane & 15);
-#pragma unroll 1
-  for (int s0 = 0; s0 < NJ; s0 += B) {
-    float vj[B];
-    float4 a[B][FE / 4];
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-      vj[b] = vp[4 * (s0 + b)];
-#pragma unroll
-      for (int e = 0; e < FE / 4; ++e) a[b][e] = *reinterpret_cast<const float4 *>(row + (size_t)4 * (s0 + b) * lda + 64 * e);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-#pragma unroll
-      for (int e = 0; e < FE / 4; ++e) {
-        ae[4 * e] = fmaf(vj[b], a[b][e].x, ae[4 * e]);
-        ae[4 * e + 1] = fmaf(vj[b], a[b][e].y, ae[4 * e + 1]);
-        ae[4 * e + 2] = fmaf(vj[b], a[b][e].z, ae[4 * e + 2]);
-        ae[4 * e + 3] = fmaf(vj[b], a[b][e].w, ae[4 * e + 3]);
-      }
-    __builtin_amdgcn_sched_barrier(0);
   }
 }
 

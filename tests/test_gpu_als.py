@@ -125,6 +125,36 @@ def test_team_width_boundaries_row_by_row(gpu, oracle, f, cg_steps):
     assert not got[empty].any()
 
 
+# the cuts of the packed-fp16 team kernel (64 entries per wavefront: team widths 1 / 2 / 4 / 8 up to 64 / 128 / 256 / 512
+# nonzeros) and of the short rows (<= 32) from both sides
+HALF_TEAM_EDGE_LENGTHS = [31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 0]
+
+
+@pytest.mark.parametrize("cg_steps", [1, 3])
+@pytest.mark.parametrize("f", [128, 64])
+def test_half_team_width_boundaries_row_by_row(gpu, oracle, f, cg_steps):
+    """float16 storage: per-ROW parity at every cut of the packed 64-entry tile kernel, within 1e-3 of the oracle run on the
+    fp16-rounded inputs (the result is stored in fp16).  The oracle is handed the GPU's gramian of the fp16 factors, which
+    test_native_fp16_factor_storage pins to the fp32 gramian bit for bit.  The grid covers every row here, so each team
+    solves one row: a wrong share of the entries or of the gramian rows, or a wrong weight-table slot, shows in that row."""
+    items = 3000
+    lengths = HALF_TEAM_EDGE_LENGTHS * 7   # 7 rows per length: several workgroups per class
+    C = _edge_matrix(lengths, items, seed=f + cg_steps)
+    rng = np.random.default_rng(11)
+    Y = ((rng.random((items, f), dtype=np.float32) - 0.5) * 0.2).astype(np.float16)
+    X = ((rng.random((C.shape[0], f), dtype=np.float32) - 0.5) * 0.2).astype(np.float16)
+    got, gram = _gpu_cg(gpu, C, X.copy(), Y, 0.05, cg_steps)
+    assert got.dtype == np.float16
+    want = X.astype(np.float32)
+    oracle.least_squares_cg(C, want, Y.astype(np.float32), 0.05, cg_steps=cg_steps, YtY=gram)
+    num = np.linalg.norm(got.astype(np.float64) - want, axis=1)
+    err = num / np.maximum(np.linalg.norm(want.astype(np.float64), axis=1), 1e-30)
+    print("f", f, "cg", cg_steps, "fp16 per-row rel max %.2e" % err.max(), "at length", lengths[int(err.argmax())])
+    assert err.max() < 1e-3
+    empty = np.asarray(lengths) == 0
+    assert not got[empty].any()
+
+
 def test_cg_long_rows_and_edge_cases(gpu, oracle):
     """Rows long enough for the workgroup-per-row class, empty rows, explicit zeros, negatives."""
     rng = np.random.default_rng(3)
