@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/implicit_hip.h"
+#include "csr_schedule.h"
 
 namespace imp {
 
@@ -237,7 +238,15 @@ struct LongPlan {
   int32_t n_long = 0, n_seg = 0;
   imp::DeviceArray<int32_t> row_seg, seg_row, seg_begin, seg_end, seg_exec;
   int32_t xcd_start[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t stripe = 0;  // column-stripe width (0: rows cut into plain kSegment runs)
+  void upload(const imp::HostPlan &p) {  // queued on the library stream: `p` has to outlive the next sync()
+    n_long = p.n_long, n_seg = p.n_seg;
+    seg_exec.upload(p.seg_exec.data(), p.seg_exec.size());
+    row_seg.upload(p.row_seg.data(), p.row_seg.size());
+    seg_row.upload(p.seg_row.data(), p.seg_row.size());
+    seg_begin.upload(p.seg_begin.data(), p.seg_begin.size());
+    seg_end.upload(p.seg_end.data(), p.seg_end.size());
+    for (int x = 0; x < 9; ++x) xcd_start[x] = p.xcd_start[x];
+  }
   LongPlanDev dev(const int32_t *rows) const {
     LongPlanDev d{n_long, n_seg, rows, row_seg.data(), seg_row.data(), seg_begin.data(), seg_end.data(), seg_exec.data(), {0}};
     for (int x = 0; x < 9; ++x) d.xcd_start[x] = xcd_start[x];
@@ -250,30 +259,23 @@ struct LongPlan {
 // class b covers order[bin_start[b] .. bin_start[b+1]) and holds the rows with
 // kClassMax[b+1] < nnz <= kClassMax[b]:
 //   0 long  (> 512 nnz): cut into segments of <= kSegment nnz (column-striped when the rows re-use the gathered
-//        matrix enough, see imp_csr_create), segment-parallel CG passes
+//        matrix enough, see build_plan in csr_schedule.hip), segment-parallel CG passes
 //   1..4 mid (256,512], (128,256], (64,128], (32,64]: a TEAM of 16/8/4/2 wavefronts per row, every
 //        wavefront keeps one 32-row gathered tile in registers for all passes
 //   5 short (16,32] and 6 short (0,16]: one wavefront per row, resident tile of 32 / 16 entries, 16 rows per
 //        workgroup in lock step (MFMA gramian product)
 //   7 empty
-struct imp_csr {
-  static constexpr int kBins = 8;
-  static constexpr int kShortRow = 32;
-  static constexpr int kLongRow = 512;
-  static constexpr int kSegment = 512;
-  static constexpr int32_t kClassMax[kBins + 1] = {INT32_MAX, 512, 256, 128, 64, 32, 16, 0, -1};
+struct imp_csr : imp::CsrClasses {
   int32_t rows = 0, cols = 0;
   int64_t nnz = 0;
   imp::DeviceArray<int32_t> indptr, indices;
   imp::DeviceArray<float> data;
   imp::DeviceArray<int32_t> order;
   int32_t bin_start[kBins + 1] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t max_row = 0;
   // long-row plans: `plan_all` covers every row of class 0 (> kLongRow nonzeros) and is what the generic kernels (and the f = 64 /
   // 128 path under IMP_NM=0) stream.  Rows of more than kCholLongRow nonzeros (the first n_chol_long entries of `order`) cut into
   // plain runs of kCholSegment: the A-build of the f = 64 Cholesky kernel is segment-parallel for them (als_cholesky.hip)
   LongPlan plan_all;
-  static constexpr int kCholLongRow = 1024, kCholSegment = 1024;
   LongPlan plan_chol;
   int32_t n_chol_long = 0;
   // every row of class 0 cut into plain runs of `nm_segment` nonzeros (2048 .. 16384: about eight segments per CU and launch, so

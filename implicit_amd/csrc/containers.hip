@@ -7,7 +7,6 @@
 #include <hip/hip_fp16.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -535,6 +534,36 @@ int imp_host_csr_transpose(int32_t rows, int32_t cols, int64_t nnz, const int32_
   });
 }
 
+// ---- host-side helper: the schedule imp_csr_create builds, returned to the caller ---------------------
+// Validation and planner are the functions imp_csr_create calls (csr_schedule.hip); the knobs are arguments here, not the
+// environment.  `which` picks the long-row plan that is copied out: 0 plan_all, 1 plan_chol, 2 plan_nm.
+int imp_host_csr_plan(int32_t rows, int32_t cols, const int32_t *indptr, const int32_t *indices, int32_t segment, int32_t stripe,
+                      int32_t nm_segment, int32_t num_cus, int which, int32_t *order, int32_t *bin_start, int32_t *row_seg,
+                      int64_t seg_capacity, int32_t *seg_row, int32_t *seg_begin, int32_t *seg_end, int32_t *seg_exec,
+                      int32_t *xcd_start, int32_t *info) {
+  return guarded_host([&] {
+    if (which < 0 || which > 2) throw std::invalid_argument("host_csr_plan: which must be 0 (all), 1 (chol) or 2 (nm)");
+    if (nm_segment < 0) throw std::invalid_argument("host_csr_plan: nm_segment must be positive, or 0 for the automatic length");
+    if (rows < 0) throw std::invalid_argument("negative dimension for CSRMatrix");
+    validate_csr(rows, cols, rows ? (int64_t)indptr[rows] : 0, indptr, indices);
+    PlanKnobs knobs;
+    knobs.segment = segment, knobs.stripe = stripe, knobs.nm_segment = nm_segment, knobs.num_cus = num_cus;
+    const HostSchedule s = plan_csr(rows, cols, indptr, indices, knobs);
+    const HostPlan &p = which == 0 ? s.plan_all : which == 1 ? s.plan_chol : s.plan_nm;
+    if (p.n_seg > seg_capacity) throw std::invalid_argument("host_csr_plan: the plan has more segments than seg_capacity");
+    std::copy(s.order.begin(), s.order.end(), order);
+    std::copy(s.bin_start, s.bin_start + imp_csr::kBins + 1, bin_start);
+    std::copy(p.row_seg.begin(), p.row_seg.end(), row_seg);
+    std::copy(p.seg_row.begin(), p.seg_row.end(), seg_row);
+    std::copy(p.seg_begin.begin(), p.seg_begin.end(), seg_begin);
+    std::copy(p.seg_end.begin(), p.seg_end.end(), seg_end);
+    std::copy(p.seg_exec.begin(), p.seg_exec.end(), seg_exec);
+    std::copy(p.xcd_start, p.xcd_start + 9, xcd_start);
+    const int32_t fields[8] = {p.n_long, p.n_seg, p.striped, s.n_chol_long, s.nm_segment, s.nm_multi_rows, s.nm_multi_segs, 0};
+    std::copy(fields, fields + 8, info);
+  });
+}
+
 // ---- Matrix -------------------------------------------------------------------------------------
 int imp_matrix_create(size_t rows, size_t cols, const void *host_data, size_t itemsize, imp_matrix **out) {
   return guarded([&] {
@@ -739,208 +768,46 @@ int imp_intvector_destroy(imp_intvector *v) {
 }
 
 // ---- CSR / COO -----------------------------------------------------------------------------------
+// IMP_SEGMENT / IMP_STRIPE / IMP_NM_SEGMENT: segment length and column-stripe width of the streamed long-row plan, segment
+// length of the normal-matrix work list (read per CSRMatrix; unset = the planner's defaults)
+static PlanKnobs plan_knobs_from_env() {
+  PlanKnobs k;
+  if (const char *e = getenv("IMP_SEGMENT")) k.segment = std::max(32, atoi(e));
+  if (const char *e = getenv("IMP_STRIPE")) k.stripe = std::max(0, atoi(e));
+  if (const char *e = getenv("IMP_NM_SEGMENT")) k.nm_segment = std::max(64, atoi(e));
+  k.num_cus = ctx().num_cus;
+  return k;
+}
+
+// a validated matrix (or row block) -> device arrays and schedule
+static std::unique_ptr<imp_csr> make_csr(int32_t rows, int32_t cols, int64_t nnz, const int32_t *indptr, const int32_t *indices,
+                                         const float *data, const PlanKnobs &knobs) {
+  auto m = std::make_unique<imp_csr>();
+  m->rows = rows;
+  m->cols = cols;
+  m->nnz = nnz;
+  m->indptr.upload(indptr, (size_t)rows + 1);
+  m->indices.upload(indices, (size_t)nnz);
+  m->data.upload(data, (size_t)nnz);
+  const HostSchedule s = plan_csr(rows, cols, indptr, indices, knobs);
+  m->order.upload(s.order.data(), s.order.size());
+  std::copy(s.bin_start, s.bin_start + imp_csr::kBins + 1, m->bin_start);
+  m->plan_all.upload(s.plan_all);
+  m->plan_chol.upload(s.plan_chol);
+  m->plan_nm.upload(s.plan_nm);
+  m->n_chol_long = s.n_chol_long;
+  m->nm_segment = s.nm_segment;
+  m->nm_multi_rows = s.nm_multi_rows;
+  m->nm_multi_segs = s.nm_multi_segs;
+  sync();  // the uploads read pageable host memory: the schedule's vectors (and the caller's arrays) live until here
+  return m;
+}
+
 int imp_csr_create(int32_t rows, int32_t cols, int64_t nnz, const int32_t *indptr, const int32_t *indices,
                    const float *data, imp_csr **out) {
   return guarded([&] {
-    constexpr bool timing = false;  // (debug: where the construction time goes, on stderr)
-    auto t_mark = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-      if (!timing) return;
-      sync();
-      auto now = std::chrono::steady_clock::now();
-      fprintf(stderr, "[csr-timing] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_mark).count());
-      t_mark = now;
-    };
-    if (rows < 0 || cols < 0 || nnz < 0) throw std::invalid_argument("negative dimension for CSRMatrix");
-    if (nnz > INT32_MAX) throw std::invalid_argument("CSRMatrix with more than 2^31-1 nonzeros is not supported");
-    if (rows && indptr[rows] != nnz) throw std::invalid_argument("indptr[rows] != nonzeros for CSRMatrix");
-    if (rows && indptr[0] != 0) throw std::invalid_argument("indptr[0] != 0 for CSRMatrix");
-    // a malformed matrix would turn into out-of-bounds gathers on the device: indptr must not decrease, column ids
-    // must lie in [0, cols) (scipy's check_format(full_check=True) conditions; one pass over the host arrays)
-    for (int32_t r = 0; r < rows; ++r)
-      if (indptr[r + 1] < indptr[r]) throw std::invalid_argument("indptr must be non-decreasing for CSRMatrix (row " + std::to_string(r) + ")");
-    {
-      int32_t lo = 0, hi = -1;
-      for (int64_t k = 0; k < nnz; ++k) {
-        lo = std::min(lo, indices[k]);
-        hi = std::max(hi, indices[k]);
-      }
-      if (nnz && (lo < 0 || hi >= cols))
-        throw std::invalid_argument("column index out of range for CSRMatrix (" + std::to_string(lo < 0 ? lo : hi) + " not in [0, " +
-                                    std::to_string(cols) + "))");
-    }
-    lap("validation");
-    auto m = std::make_unique<imp_csr>();
-    m->rows = rows;
-    m->cols = cols;
-    m->nnz = nnz;
-    m->indptr.upload(indptr, (size_t)rows + 1);
-    m->indices.upload(indices, (size_t)nnz);
-    m->data.upload(data, (size_t)nnz);
-    lap("upload indptr/indices/data");
-
-    // Row schedule: counting sort of row ids by descending length, cut into length classes.
-    int32_t segment = imp_csr::kSegment;
-    if (const char *e = getenv("IMP_SEGMENT")) segment = std::max(32, atoi(e));
-    int32_t max_len = 0;
-    for (int32_t r = 0; r < rows; ++r) max_len = std::max(max_len, indptr[r + 1] - indptr[r]);
-    m->max_row = max_len;
-    std::vector<int32_t> count((size_t)max_len + 2, 0);
-    for (int32_t r = 0; r < rows; ++r) count[indptr[r + 1] - indptr[r]]++;
-    std::vector<int32_t> start((size_t)max_len + 2, 0);
-    int32_t acc = 0;
-    int32_t class_count[imp_csr::kBins] = {0};
-    for (int32_t len = max_len; len >= 0; --len) {
-      start[len] = acc;
-      acc += count[len];
-      int b = 0;
-      while (len <= imp_csr::kClassMax[b + 1]) ++b;  // kClassMax[b+1] < len <= kClassMax[b]
-      class_count[b] += count[len];
-    }
-    std::vector<int32_t> order((size_t)rows);
-    for (int32_t r = 0; r < rows; ++r) order[start[indptr[r + 1] - indptr[r]]++] = r;
-    m->order.upload(order.data(), order.size());
-    lap("row schedule (counting sort)");
-    m->bin_start[0] = 0;
-    for (int b = 0; b < imp_csr::kBins; ++b) m->bin_start[b + 1] = m->bin_start[b] + class_count[b];
-    const int32_t n_long = class_count[0];
-
-    // long rows -> segments.
-    //
-    // Plain plan: consecutive runs of <= kSegment nonzeros.  Striped plan: the long rows of a popular-item side gather
-    // the SAME factor rows over and over (C3 item side: 3.3 M long-row nonzeros over 359 K columns), but a plain
-    // segment spans far more of the factor matrix than an L2 holds, so every pass streams them from the
-    // Infinity Cache / HBM again.  If the rows are column-sorted and the re-use is >= 4, rows are cut at multiples of
-    // `stripe` columns instead; the stripes are dealt to the 8 XCDs (greedy by weight) and each XCD's workgroups
-    // (blockIdx % 8) sweep their stripes one after the other, so that the 2 MB of factor rows a stripe covers are
-    // fetched into that XCD's L2 and hit by every long row (measured: partial kernel 2.6x faster with fully
-    // L2-resident gathers; 1.3x with the real plan, whose segments are short).  Segments stay in row-major order (the combine kernel sums a row's partials in that fixed
-    // order); `seg_exec` is the execution order.
-    // width: 12288 columns (6 MB of factor rows at f = 128) was the best of {2048 .. 32768} on C3 (359 K columns; narrower
-    // = more, shorter segments), 6144 the best of {2048 .. 12288} on the ml-20m shape (138 K columns: the 8 XCDs need
-    // enough stripes to balance) -- hence about 24 stripes, between 4096 and 12288 columns
-    int32_t stripe = std::min(12288, std::max(4096, (cols / 24 + 1023) / 1024 * 1024));
-    if (const char *e = getenv("IMP_STRIPE")) stripe = std::max(0, atoi(e));
-    double stripe_reuse = 4.0;  // minimum gathers per column of the gathered matrix for the striped plan
-    auto build_plan = [&](int32_t n_plan, LongPlan &lp, double stripe_reuse, int32_t segment) {
-      int64_t long_nnz = 0;
-      bool sorted = true;
-      for (int32_t li = 0; li < n_plan; ++li) {
-        const int32_t r = order[li];
-        long_nnz += indptr[r + 1] - indptr[r];
-        if (stripe > 0 && sorted) sorted = std::is_sorted(indices + indptr[r], indices + indptr[r + 1]);
-      }
-      // ... and only when a row still leaves >= 32 nonzeros per stripe on average: with many more stripes than that (configs[3]'s
-      // item side: 10 M columns = 814 stripes under rows of ~800 nonzeros) the cut would produce one- and two-entry segments,
-      // hundreds of millions of them (23 s of plan building before this rule)
-      const int64_t n_stripes_all = stripe > 0 ? ((int64_t)cols + stripe - 1) / stripe : 1;
-      const bool striped = stripe > 0 && sorted && n_plan > 0 && (double)long_nnz >= stripe_reuse * (double)cols &&
-                           (double)long_nnz >= 32.0 * (double)n_stripes_all * (double)n_plan;
-      std::vector<int32_t> row_seg((size_t)n_plan + 1, 0), seg_row, seg_begin, seg_end, seg_stripe;
-      for (int32_t li = 0; li < n_plan; ++li) {
-        const int32_t r = order[li];
-        row_seg[li] = (int32_t)seg_row.size();
-        int32_t pos = indptr[r];
-        const int32_t row_end = indptr[r + 1];
-        while (pos < row_end) {
-          int32_t hi = row_end, st = 0;
-          if (striped) {
-            st = indices[pos] / stripe;
-            const int64_t bound = ((int64_t)st + 1) * stripe;
-            hi = (int32_t)(std::lower_bound(indices + pos, indices + row_end, bound,
-                                            [](int32_t c, int64_t b) { return (int64_t)c < b; }) -
-                           indices);
-          }
-          for (int32_t b = pos; b < hi; b += segment) {
-            seg_row.push_back(li);
-            seg_begin.push_back(b);
-            seg_end.push_back(std::min(hi, b + segment));
-            seg_stripe.push_back(st);
-          }
-          pos = hi;
-        }
-      }
-      row_seg[n_plan] = (int32_t)seg_row.size();
-      const int32_t n_seg = (int32_t)seg_row.size();
-      std::vector<int32_t> seg_exec((size_t)n_seg);
-      if (striped) {
-        const int32_t n_stripes = (cols + stripe - 1) / stripe;
-        std::vector<int64_t> weight((size_t)n_stripes, 0);
-        for (int32_t s = 0; s < n_seg; ++s) weight[seg_stripe[s]] += seg_end[s] - seg_begin[s] + 16;  // + per-segment overhead
-        std::vector<int32_t> by_weight((size_t)n_stripes);
-        for (int32_t i = 0; i < n_stripes; ++i) by_weight[i] = i;
-        std::stable_sort(by_weight.begin(), by_weight.end(), [&](int32_t a, int32_t b) { return weight[a] > weight[b]; });
-        int64_t load[8] = {0};
-        std::vector<int32_t> stripe_xcd((size_t)n_stripes, 0), stripe_rank((size_t)n_stripes, 0);
-        int32_t per_xcd[8] = {0};
-        for (int32_t st : by_weight) {  // heaviest first onto the least loaded XCD
-          int x = (int)(std::min_element(load, load + 8) - load);
-          load[x] += weight[st];
-          stripe_xcd[st] = x;
-          stripe_rank[st] = per_xcd[x]++;
-        }
-        std::vector<int32_t> ids((size_t)n_seg);
-        for (int32_t s = 0; s < n_seg; ++s) ids[s] = s;
-        std::stable_sort(ids.begin(), ids.end(), [&](int32_t a, int32_t b) {
-          const int32_t sa = seg_stripe[a], sb = seg_stripe[b];
-          if (stripe_xcd[sa] != stripe_xcd[sb]) return stripe_xcd[sa] < stripe_xcd[sb];
-          return stripe_rank[sa] < stripe_rank[sb];  // equal stripe: ascending segment id = ascending row
-        });
-        seg_exec = ids;
-        int32_t posx = 0;
-        for (int x = 0; x < 8; ++x) {
-          lp.xcd_start[x] = posx;
-          while (posx < n_seg && stripe_xcd[seg_stripe[seg_exec[posx]]] == x) ++posx;
-        }
-        lp.xcd_start[8] = n_seg;
-        lp.stripe = stripe;
-      } else {
-        // plain plan: runs of 4 consecutive segments dealt round-robin to the XCDs (neighbouring segments of a row,
-        // i.e. neighbouring column ranges, stay on one XCD)
-        int32_t posx = 0;
-        for (int x = 0; x < 8; ++x) {
-          lp.xcd_start[x] = posx;
-          for (int32_t s = 0; s < n_seg; ++s)
-            if ((s / 4) % 8 == x) seg_exec[posx++] = s;
-        }
-        lp.xcd_start[8] = n_seg;
-      }
-      lp.n_long = n_plan;
-      lp.n_seg = n_seg;
-      lp.seg_exec.upload(seg_exec.data(), seg_exec.size());
-      lp.row_seg.upload(row_seg.data(), row_seg.size());
-      lp.seg_row.upload(seg_row.data(), seg_row.size());
-      lp.seg_begin.upload(seg_begin.data(), seg_begin.size());
-      lp.seg_end.upload(seg_end.data(), seg_end.size());
-      sync();  // the uploads read pageable host vectors that die with this scope
-    };
-    build_plan(n_long, m->plan_all, stripe_reuse, segment);
-    lap("long-row plan (all)");
-    // rows of more than kCholLongRow nonzeros: the first n_chol_long entries of `order` (sorted by descending length)
-    {
-      int32_t longer = 0;
-      for (int32_t len = max_len; len > imp_csr::kCholLongRow; --len) longer += count[len];
-      m->n_chol_long = longer;
-    }
-    build_plan(m->n_chol_long, m->plan_chol, 1e30, imp_csr::kCholSegment);  // never striped
-    {
-      int64_t long_nnz = 0;
-      for (int32_t li = 0; li < n_long; ++li) long_nnz += indptr[order[li] + 1] - indptr[order[li]];
-      int32_t seg = 2048;
-      while (seg < 16384 && (int64_t)seg * ctx().num_cus * 8 < long_nnz) seg *= 2;
-      if (const char *e = getenv("IMP_NM_SEGMENT")) seg = std::max(64, atoi(e));
-      m->nm_segment = seg;
-      for (int32_t li = 0; li < n_long; ++li) {
-        const int32_t len = indptr[order[li] + 1] - indptr[order[li]];
-        if (len <= seg) break;  // descending lengths
-        m->nm_multi_rows++;
-        m->nm_multi_segs += (len + seg - 1) / seg;
-      }
-      build_plan(n_long, m->plan_nm, 1e30, seg);  // never striped: a row's segments are consecutive runs
-    }
-    sync();
-    lap("long-row plans (xl, chol, nm)");
-    *out = m.release();
+    validate_csr(rows, cols, nnz, indptr, indices);
+    *out = make_csr(rows, cols, nnz, indptr, indices, data, plan_knobs_from_env()).release();
   });
 }
 
@@ -950,21 +817,15 @@ int imp_csr_create(int32_t rows, int32_t cols, int64_t nnz, const int32_t *indpt
 int imp_csr_create64(int32_t rows, int32_t cols, int64_t nnz, const int64_t *indptr, const int32_t *indices, const float *data,
                      imp_csr **out) {
   return guarded([&] {
-    if (rows < 0 || cols < 0 || nnz < 0) throw std::invalid_argument("negative dimension for CSRMatrix");
-    if (rows && indptr[rows] != nnz) throw std::invalid_argument("indptr[rows] != nonzeros for CSRMatrix");
-    if (rows && indptr[0] != 0) throw std::invalid_argument("indptr[0] != 0 for CSRMatrix");
-    for (int32_t r = 0; r < rows; ++r)
-      if (indptr[r + 1] < indptr[r]) throw std::invalid_argument("indptr must be non-decreasing for CSRMatrix (row " + std::to_string(r) + ")");
+    validate_csr(rows, cols, nnz, indptr, indices);
     int64_t part_limit = INT32_MAX;
     if (const char *e = getenv("IMP_CSR_PART_NNZ")) part_limit = std::max<int64_t>(1, std::min<int64_t>(INT32_MAX, atoll(e)));
+    const PlanKnobs knobs = plan_knobs_from_env();
     auto build = [&](int32_t r0, int32_t r1) {
       std::vector<int32_t> local((size_t)(r1 - r0) + 1);
       const int64_t base = indptr[r0];
       for (int32_t r = r0; r <= r1; ++r) local[r - r0] = (int32_t)(indptr[r] - base);
-      imp_csr *part = nullptr;
-      if (imp_csr_create(r1 - r0, cols, indptr[r1] - base, local.data(), indices + base, data + base, &part) != IMP_OK)
-        throw std::invalid_argument(imp_last_error());
-      return std::unique_ptr<imp_csr>(part);
+      return make_csr(r1 - r0, cols, indptr[r1] - base, local.data(), indices + base, data + base, knobs);
     };
     if (nnz <= part_limit) {
       *out = build(0, rows).release();
@@ -978,7 +839,6 @@ int imp_csr_create64(int32_t rows, int32_t cols, int64_t nnz, const int64_t *ind
       if (r1 == r0) throw std::invalid_argument("a single row exceeds the per-block nonzero limit of CSRMatrix");
       top->part_row0.push_back(r0);
       top->parts.push_back(build(r0, r1));
-      top->max_row = std::max(top->max_row, top->parts.back()->max_row);
       r0 = r1;
     }
     *out = top.release();

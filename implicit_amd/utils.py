@@ -100,3 +100,31 @@ def transpose_csr(m, threads=0):
     out.has_sorted_indices = True
     out.has_canonical_format = True
     return out
+
+
+def csr_schedule(m, which=0, segment=512, stripe=-1, nm_segment=0, num_cus=256):
+    """The row schedule and one long-row plan `CSRMatrix(m)` would build, computed on the host (imp_host_csr_plan: the
+    planner of imp_csr_create with its knobs as arguments, no device involved).  `which`: 0 the streamed plan, 1 the
+    Cholesky plan, 2 the normal-matrix work list; stripe < 0 and nm_segment 0 select the automatic values.  Returns a dict
+    of numpy arrays (order, bin_start, row_seg, seg_row, seg_begin, seg_end, seg_exec, xcd_start) and the scalars n_long,
+    n_seg, striped, n_chol_long, nm_segment, nm_multi_rows, nm_multi_segs."""
+    from .gpu._hip import check, lib
+
+    rows, cols = m.shape
+    indptr = np.ascontiguousarray(m.indptr, dtype=np.int32)
+    indices = np.ascontiguousarray(m.indices, dtype=np.int32)
+    capacity = max(int(indptr[-1]), 0) if rows else 0
+    out = {"order": np.empty(rows, np.int32), "bin_start": np.empty(9, np.int32), "row_seg": np.empty(rows + 1, np.int32)}
+    segs = {k: np.empty(capacity, np.int32) for k in ("seg_row", "seg_begin", "seg_end", "seg_exec")}
+    out["xcd_start"] = np.empty(9, np.int32)
+    info = np.zeros(8, np.int32)
+    check(lib().imp_host_csr_plan(rows, cols, indptr.ctypes.data, indices.ctypes.data, segment, stripe, nm_segment, num_cus, which,
+                                  out["order"].ctypes.data, out["bin_start"].ctypes.data, out["row_seg"].ctypes.data, capacity,
+                                  *(segs[k].ctypes.data for k in ("seg_row", "seg_begin", "seg_end", "seg_exec")),
+                                  out["xcd_start"].ctypes.data, info.ctypes.data))
+    names = ("n_long", "n_seg", "striped", "n_chol_long", "nm_segment", "nm_multi_rows", "nm_multi_segs")
+    out.update({k: int(v) for k, v in zip(names, info)})
+    out["striped"] = bool(out["striped"])
+    out["row_seg"] = out["row_seg"][:out["n_long"] + 1]
+    out.update({k: v[:out["n_seg"]] for k, v in segs.items()})
+    return out

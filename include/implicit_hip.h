@@ -91,6 +91,21 @@ const char *imp_version(void);
 int imp_host_csr_transpose(int32_t rows, int32_t cols, int64_t nonzeros, const int32_t *indptr, const int32_t *indices,
                            const float *data, int32_t *t_indptr, int32_t *t_indices, float *t_data, int threads);
 
+/* NEW, host-side helper (no device work, usable without a GPU): the row schedule and one long-row plan exactly as
+ * imp_csr_create builds them, with the knobs as arguments: segment (nonzeros per segment of the streamed plan; IMP_SEGMENT),
+ * stripe (its column-stripe width; < 0 automatic, 0 never striped; IMP_STRIPE), nm_segment (segment of the normal-matrix work
+ * list; 0 automatic; IMP_NM_SEGMENT), num_cus (compute units the automatic nm_segment is sized for).  which: 0 the streamed
+ * plan of every row > 512 nonzeros, 1 the Cholesky plan of the rows > 1024, 2 the normal-matrix work list.  Outputs are
+ * caller-allocated: order[rows] (row ids by descending length), bin_start[9] (length classes of `order`), row_seg[rows + 1] (the
+ * first n_long + 1 entries are written), seg_row / seg_begin / seg_end / seg_exec[seg_capacity] (n_seg entries are written; a
+ * segment holds at least one nonzero, so indptr[rows] always suffices; IMP_INVALID_ARGUMENT if the plan does not fit),
+ * xcd_start[9], info[8] = {n_long, n_seg, striped, n_chol_long, nm_segment, nm_multi_rows, nm_multi_segs, 0}.  The matrix is
+ * validated as by imp_csr_create. */
+int imp_host_csr_plan(int32_t rows, int32_t cols, const int32_t *indptr, const int32_t *indices, int32_t segment, int32_t stripe,
+                      int32_t nm_segment, int32_t num_cus, int which, int32_t *order, int32_t *bin_start, int32_t *row_seg,
+                      int64_t seg_capacity, int32_t *seg_row, int32_t *seg_begin, int32_t *seg_end, int32_t *seg_exec,
+                      int32_t *xcd_start, int32_t *info);
+
 /* ---- Matrix (matrix.h:23-90, matrix.cu:34-220) -------------------------------------------- */
 /* Matrix(rows, cols, data, allocate=true, itemsize): allocates; copies rows*cols*itemsize bytes
  * from host_data when non-NULL, zero-fills otherwise (matrix.cu:80-96). */
