@@ -73,7 +73,7 @@ static void launch_qfteam(const imp_csr *C, int first, int count, T *X, const T 
 // The waves publish their operands in LDS; the dense part of a pass is ONE product A0 . P^T for the 16 rows, its 16-factor output
 // tiles x K-slices dealt to the 16 waves, the results back through LDS.  Round 3 on top of it:
 //   * the operand a wave has just published is read back EXPANDED (two ds_read_b128) instead of 6 permlane swaps;
-//   * weight table, pair-wise DPP reduction, v_rcp divisions, x-only last step as in the team kernel;
+//   * weight table, pair-wise DPP reduction, v_rcp divisions, last step on the scalar p . A p as in the team kernel;
 //   * rolling gather: a workgroup holds its CU alone (its LDS), so while its 16 waves waited for the gathers of a new group of
 //     rows the CU did nothing; the last pass of a group now re-fills each pair of tile registers with the next group's entries
 //     as soon as the pair is done;
@@ -104,12 +104,16 @@ __device__ __forceinline__ void split_bf16(float x, __bf16 &hi, __bf16 &mid, __b
 
 // tile part of a pass: acc (compact) = sum over the resident entries of w y, operand read expanded from `vrow` (natural order)
 //   FIRST: w = c+ - (|c|-1) y.x   else: w = (|c|-1) y.v
-template <int F, bool FIRST, bool LAST, typename ST>
-__device__ __forceinline__ void tile_pass(f32x2 (&y)[8][F / 32], float *cw, int cnt, const float *vrow, float (&acc)[F / 64], int lane,
+//   LAST : the last CG step needs p . A p only (fused_pass): no weights, no axpys, acc is left alone; RETURNS this lane's share
+//          of sum (|c|-1) (y . p)^2 -- the sum of the shares over the wave is the tile part of p . A p
+//   ROLL : pair P of the tile is re-filled with the next group's entries once it is done (with LAST only)
+template <int F, bool FIRST, bool LAST, bool ROLL, typename ST>
+__device__ __forceinline__ float tile_pass(f32x2 (&y)[8][F / 32], float *cw, int cnt, const float *vrow, float (&acc)[F / 64], int lane,
                                           int cnt_nx, int &col_nx, float &c_nx, const ST *__restrict__ Y) {
   using Tile = Tile32<ST>;
   constexpr int FE = F / 16, H = FE / 2;
-  if constexpr (LAST) {  // one wait for the staged entries, before any rolling gather (fused_pass)
+  static_assert(!(FIRST && LAST) && (LAST || !ROLL), "pass form");
+  if constexpr (ROLL) {  // one wait for the staged entries, before any rolling gather (fused_pass)
     col_nx = opaque(col_nx);
     c_nx = __int_as_float(opaque(__float_as_int(c_nx)));
   }
@@ -124,31 +128,43 @@ __device__ __forceinline__ void tile_pass(f32x2 (&y)[8][F / 32], float *cw, int 
       ve[e / 2] = f32x2{t.x, t.y}, ve[e / 2 + 1] = f32x2{t.z, t.w};
     }
     cwg = cw + g;
+    if constexpr (LAST) cwg += 4 * (m >> 3);  // the weight of the total this lane holds after reduce_pair
   }
 #pragma unroll
   for (int h = 0; h < H; ++h) ae[h] = f32x2{0.f, 0.f};
+  float s8 = 0.f;  // LAST: every entry is counted in 8 lanes
   auto partial = [&](int q) { return Tile::template dot<H>(y[q], ve); };
   auto axpy = [&](int q, float w) { Tile::template axpy<H>(y[q], w, ae); };
   static_for<4>([&](auto Pc) {
     constexpr int P = decltype(Pc)::value;
     if (8 * P < cnt) {  // wave-uniform
-      const float cm1_0 = cwg[8 * P], cm1_1 = cwg[8 * P + 4];
-      float cp_0 = 0.f, cp_1 = 0.f;
+      const float cm1_0 = cwg[8 * P];
+      float cm1_1 = 0.f, cp_0 = 0.f, cp_1 = 0.f;
+      if constexpr (!LAST) cm1_1 = cwg[8 * P + 4];
       if constexpr (FIRST) cp_0 = cwg[32 + 8 * P], cp_1 = cwg[32 + 8 * P + 4];
       const float u = reduce_pair(partial(2 * P), partial(2 * P + 1));
-      const float w0 = FIRST ? fmaf(-cm1_0, row_bcast_from<0>(u), cp_0) : cm1_0 * row_bcast_from<0>(u);
-      const float w1 = FIRST ? fmaf(-cm1_1, row_bcast_from<8>(u), cp_1) : cm1_1 * row_bcast_from<8>(u);
-      axpy(2 * P, w0);
-      axpy(2 * P + 1, w1);
+      if constexpr (LAST) {
+        s8 = fmaf(cm1_0 * u, u, s8);
+      } else {
+        const float w0 = FIRST ? fmaf(-cm1_0, row_bcast_from<0>(u), cp_0) : cm1_0 * row_bcast_from<0>(u);
+        const float w1 = FIRST ? fmaf(-cm1_1, row_bcast_from<8>(u), cp_1) : cm1_1 * row_bcast_from<8>(u);
+        axpy(2 * P, w0);
+        axpy(2 * P + 1, w1);
+      }
     }
-    if constexpr (LAST) {
+    if constexpr (ROLL) {
       if (8 * P < cnt_nx) gather_pair<Tile, F, P>(y, cw, col_nx, c_nx, cnt_nx, Y, lane);
     }
   });
-  float aes[FE];
+  if constexpr (LAST) {
+    return 0.125f * s8;
+  } else {
+    float aes[FE];
 #pragma unroll
-  for (int h = 0; h < H; ++h) aes[2 * h] = ae[h].x, aes[2 * h + 1] = ae[h].y;
-  reduce_expanded<F>(aes, acc);
+    for (int h = 0; h < H; ++h) aes[2 * h] = ae[h].x, aes[2 * h + 1] = ae[h].y;
+    reduce_expanded<F>(aes, acc);
+    return 0.f;
+  }
 }
 
 template <int F, typename ST>
@@ -287,9 +303,9 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
     for (int cc = 0; cc < FC; ++cc) xc[cc] = x[cc];
     // r = -(A0 x) + sum_k (c+ - (|c|-1) y.x) y        (_als.pyx:187-201)
     publish(xc, valid);
-    if (!product_first) tile_pass<F, true, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
+    if (!product_first) tile_pass<F, true, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
     product();
-    if (product_first) tile_pass<F, true, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
+    if (product_first) tile_pass<F, true, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
     __syncthreads();
     collect(Ap);
 #pragma unroll
@@ -299,9 +315,9 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
     const bool store = active;
     for (int it = 0; it + 1 < cg_steps; ++it) {  // all steps but the last; every wave takes the barriers
       publish(p, active);
-      if (active && !product_first) tile_pass<F, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
+      if (active && !product_first) tile_pass<F, false, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
       product();
-      if (active && product_first) tile_pass<F, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
+      if (active && product_first) tile_pass<F, false, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
       __syncthreads();
       collect(Ap);
       if (active) {  // wave-uniform
@@ -324,14 +340,16 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
         }
       }
     }
-    // last step: only its x update is evaluated (_als.pyx:226-241 compute r, rsnew, p that nothing reads); its tile pass
-    // rolls the next group's entries in
+    // last step: only its x update is evaluated (_als.pyx:226-241 compute r, rsnew, p that nothing reads), and that needs the
+    // scalar p . A p alone: the tile pass hands in its part as one value per lane, the 16-row product stays as it is; its
+    // tile pass rolls the next group's entries in
     bool rolled = false;
     if (cg_steps > 0) {
       publish(p, active);
+      float tile_pAp = 0.f;
       auto last_tiles = [&]() {
-        if constexpr (ROLL) tile_pass<F, false, true, ST>(y, cw, cnt, prow, sp, lane, ent_cnt, ent_col, ent_c, Y);
-        else tile_pass<F, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
+        if constexpr (ROLL) tile_pAp = tile_pass<F, false, true, true, ST>(y, cw, cnt, prow, sp, lane, ent_cnt, ent_col, ent_c, Y);
+        else tile_pAp = tile_pass<F, false, true, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
       };
       if (active && !product_first) last_tiles();
       product();
@@ -348,9 +366,8 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
         } else {
           kill(x);
         }
-#pragma unroll
-        for (int cc = 0; cc < FC; ++cc) Ap[cc] += sp[cc];
-        const float alpha = rsold * __builtin_amdgcn_rcpf(dot_compact<F>(p, Ap));
+        // p . A p = p . (A0 p) + the tile part, in one sum over the wave
+        const float alpha = rsold * __builtin_amdgcn_rcpf(wave_allsum(dot_local<FC>(p, Ap) + tile_pAp));
 #pragma unroll
         for (int cc = 0; cc < FC; ++cc) xc[cc] = fmaf(alpha, p[cc], xc[cc]);
       } else {

@@ -22,7 +22,9 @@
 //     factor order) together with a go / last / stop word; the other waves wait on the team's generation counter (an idle
 //     wave costs no issue slots -- that is the point) and read the operand back already expanded: two ds_read_b128 per
 //     lane, no swaps.  Two counters per team (arrivals A, generation B), no workgroup barrier after the prologue;
-//   * a / b by v_rcp_f32 (1 ulp) instead of the 12-instruction IEEE sequence; the last CG step only updates x;
+//   * a / b by v_rcp_f32 (1 ulp) instead of the 12-instruction IEEE sequence; the last CG step only updates x, and for that
+//     it needs the scalar p . A p alone: its pass keeps the tile's dots and drops the weight broadcasts, the axpys, the
+//     reduce-scatter and the partial VECTOR -- a wave hands the leader one float (fused_pass, LAST);
 //   * the dots of a pair of tile steps are reduced together (5 DPP adds for two values instead of 8) and the weight is
 //     applied straight from the lane that holds the total (row_newbcast operand of the multiply);
 //   * per-entry weights |c| - 1 and c+ live in an LDS table written once per row (gather_pair).
@@ -163,14 +165,21 @@ __device__ __forceinline__ void gather_pair(typename Tile::elem (&y)[Tile::T / 4
 //   FIRST: v = x, weights c+ - (|c|-1) y.x, the dense part enters negated (_als.pyx:187-201): the pass accumulates
 //          A0 x - sum w y and the caller takes the sum of the team's partials with a minus sign
 //   else : weights (|c|-1) y.v (_als.pyx:214-222)
-//   LAST : the tile registers (and weight-table slots) of pair P are re-filled with the next row's entries once the pair is done
-template <typename Tile, int F, int NJ, bool FIRST, bool LAST, typename ST>
-__device__ __forceinline__ void fused_pass(typename Tile::elem (&y)[Tile::T / 4][F / 32], float *cw, int cnt, const float *vt,
-                                           int j_begin, const float *A0s, float (&acc)[F / 64], int lane, int cnt_nx, int &col_nx,
-                                           float &c_nx, const ST *__restrict__ Y, const int32_t *__restrict__ indices,
-                                           const float *__restrict__ data, int k0_nx2, int end_nx2) {
+//   LAST : v = p of the row's last CG step, which needs alpha = rsold / (p . A p) and nothing else of A p.  The pass forms
+//          no vector: it RETURNS this wave's share of the scalar (the same value in every lane; acc is left alone),
+//              p . A p = p . (A0 p) + sum_k (|c_k|-1) (y_k . p)^2,
+//          i.e. the tile entries keep their dots and lose the weight broadcasts and the axpys, the dense ticks accumulate
+//          their gramian rows as in every pass and are dotted with the operand at the end.
+//   ROLL : the tile registers (and weight-table slots) of pair P are re-filled with the next row's entries once the pair is
+//          done (with LAST only)
+template <typename Tile, int F, int NJ, bool FIRST, bool LAST, bool ROLL, typename ST>
+__device__ __forceinline__ float fused_pass(typename Tile::elem (&y)[Tile::T / 4][F / 32], float *cw, int cnt, const float *vt,
+                                            int j_begin, const float *A0s, float (&acc)[F / 64], int lane, int cnt_nx, int &col_nx,
+                                            float &c_nx, const ST *__restrict__ Y, const int32_t *__restrict__ indices,
+                                            const float *__restrict__ data, int k0_nx2, int end_nx2) {
+  static_assert(!(FIRST && LAST) && (LAST || !ROLL), "pass form");
   constexpr int FE = F / 16, H = FE / 2, PAIRS = Tile::T / 8;
-  if constexpr (LAST) {
+  if constexpr (ROLL) {
     // The staged entries were requested a row ago.  Passing them through an opaque copy makes the compiler wait for them
     // HERE, once, while nothing else is in flight; without it every use inside the pass would wait for "all loads so far"
     // (vmcnt(0): its counter bookkeeping does not survive the branches of the pass) -- i.e. for the rolling gathers of
@@ -191,9 +200,13 @@ __device__ __forceinline__ void fused_pass(typename Tile::elem (&y)[Tile::T / 4]
     vp = vt + j_begin + g * NJ;
     row = A0s + (size_t)(j_begin + g * NJ) * F + 4 * m;
     cwg = cw + g;  // this group's entries: t = 4 q + g
+    // LAST: reduce_pair leaves the dot of step 2 P in lanes 0-7 of a row and that of step 2 P + 1 in lanes 8-15: every
+    // lane reads the one weight that belongs to the total it holds
+    if constexpr (LAST) cwg += 4 * (m >> 3);
   }
 #pragma unroll
   for (int h = 0; h < H; ++h) ae[h] = f32x2{0.f, 0.f};
+  float s8 = 0.f;  // LAST: sum of (|c|-1) (y . p)^2 over this lane's totals; every entry is counted in 8 lanes
   DenseTicks<F, NJ, 4 * PAIRS> dt;
   auto partial = [&](int q) { return Tile::template dot<H>(y[q], ve); };
   auto axpy = [&](int q, float w) { Tile::template axpy<H>(y[q], w, ae); };
@@ -201,8 +214,9 @@ __device__ __forceinline__ void fused_pass(typename Tile::elem (&y)[Tile::T / 4]
     constexpr int P = decltype(Pc)::value;
     if (8 * P < cnt) {  // wave-uniform
       dt.template issue<4 * P>(row, vp);
-      const float cm1_0 = cwg[8 * P], cm1_1 = cwg[8 * P + 4];
-      float cp_0 = 0.f, cp_1 = 0.f;
+      const float cm1_0 = cwg[8 * P];
+      float cm1_1 = 0.f, cp_0 = 0.f, cp_1 = 0.f;
+      if constexpr (!LAST) cm1_1 = cwg[8 * P + 4];
       if constexpr (FIRST) cp_0 = cwg[Tile::T + 8 * P], cp_1 = cwg[Tile::T + 8 * P + 4];
       __builtin_amdgcn_sched_barrier(0);
       const float d0 = partial(2 * P);
@@ -211,23 +225,39 @@ __device__ __forceinline__ void fused_pass(typename Tile::elem (&y)[Tile::T / 4]
       dt.template issue<4 * P + 1>(row, vp);
       __builtin_amdgcn_sched_barrier(0);
       const float d1 = partial(2 * P + 1);
-      // no fence between the reduction and the packed FMAs of the tick: they fill the wait states of its dependent DPP chain
-      const float u = reduce_pair(d0, d1);
-      dt.template consume<4 * P + 1>(ae);
-      // the whole first pass is accumulated negated: w' = (|c|-1) d - c+
-      const float w0 = FIRST ? fmaf(cm1_0, row_bcast_from<0>(u), -cp_0) : cm1_0 * row_bcast_from<0>(u);
-      const float w1 = FIRST ? fmaf(cm1_1, row_bcast_from<8>(u), -cp_1) : cm1_1 * row_bcast_from<8>(u);
-      __builtin_amdgcn_sched_barrier(0);
-      dt.template issue<4 * P + 2>(row, vp);
-      __builtin_amdgcn_sched_barrier(0);
-      axpy(2 * P, w0);
-      __builtin_amdgcn_sched_barrier(0);
-      dt.template consume<4 * P + 2>(ae);
-      dt.template issue<4 * P + 3>(row, vp);
-      __builtin_amdgcn_sched_barrier(0);
-      axpy(2 * P + 1, w1);
-      __builtin_amdgcn_sched_barrier(0);
-      dt.template consume<4 * P + 3>(ae);
+      if constexpr (LAST) {
+        // the third tick's LDS reads have the reduction to hide behind
+        __builtin_amdgcn_sched_barrier(0);
+        dt.template consume<4 * P + 1>(ae);
+        dt.template issue<4 * P + 2>(row, vp);
+        __builtin_amdgcn_sched_barrier(0);
+        // no fence between the reduction and the packed FMAs of the tick: they fill the wait states of its dependent DPP chain
+        const float u = reduce_pair(d0, d1);
+        s8 = fmaf(cm1_0 * u, u, s8);
+        dt.template consume<4 * P + 2>(ae);
+        __builtin_amdgcn_sched_barrier(0);
+        dt.template issue<4 * P + 3>(row, vp);
+        __builtin_amdgcn_sched_barrier(0);
+        dt.template consume<4 * P + 3>(ae);
+      } else {
+        // no fence between the reduction and the packed FMAs of the tick: they fill the wait states of its dependent DPP chain
+        const float u = reduce_pair(d0, d1);
+        dt.template consume<4 * P + 1>(ae);
+        // the whole first pass is accumulated negated: w' = (|c|-1) d - c+
+        const float w0 = FIRST ? fmaf(cm1_0, row_bcast_from<0>(u), -cp_0) : cm1_0 * row_bcast_from<0>(u);
+        const float w1 = FIRST ? fmaf(cm1_1, row_bcast_from<8>(u), -cp_1) : cm1_1 * row_bcast_from<8>(u);
+        __builtin_amdgcn_sched_barrier(0);
+        dt.template issue<4 * P + 2>(row, vp);
+        __builtin_amdgcn_sched_barrier(0);
+        axpy(2 * P, w0);
+        __builtin_amdgcn_sched_barrier(0);
+        dt.template consume<4 * P + 2>(ae);
+        dt.template issue<4 * P + 3>(row, vp);
+        __builtin_amdgcn_sched_barrier(0);
+        axpy(2 * P + 1, w1);
+        __builtin_amdgcn_sched_barrier(0);
+        dt.template consume<4 * P + 3>(ae);
+      }
     } else {  // no entries left: the remaining gramian rows
       // (the empty statement keeps the two branches from starting alike: the compiler otherwise hoists "read, wait,
       // consume" of the first tick above the branch and the tick's LDS latency is exposed again)
@@ -239,20 +269,31 @@ __device__ __forceinline__ void fused_pass(typename Tile::elem (&y)[Tile::T / 4]
         dt.template consume<K>(ae);
       });
     }
-    if constexpr (LAST) {
+    if constexpr (ROLL) {
       if (8 * P < cnt_nx) gather_pair<Tile, F, P>(y, cw, col_nx, c_nx, cnt_nx, Y, lane);
     }
     __builtin_amdgcn_sched_barrier(0);
   });
-  float aes[FE];
-#pragma unroll
-  for (int h = 0; h < H; ++h) aes[2 * h] = ae[h].x, aes[2 * h + 1] = ae[h].y;
-  reduce_expanded<F>(aes, acc);
+  float pAp = 0.f;
   if constexpr (LAST) {
+    // this wave's gramian rows: sum_j p_j (A0 p)_j = sum over the lanes of ae . ve, in Tile::dot's even / odd association;
+    // the tile part enters with the exact scale 1/8 that undoes its eightfold count
+    f32x2 t = ae[0] * ve[0];
+#pragma unroll
+    for (int h = 1; h < H; ++h) t = __builtin_elementwise_fma(ae[h], ve[h], t);
+    pAp = wave_allsum(fmaf(0.125f, s8, t.x + t.y));
+  } else {
+    float aes[FE];
+#pragma unroll
+    for (int h = 0; h < H; ++h) aes[2 * h] = ae[h].x, aes[2 * h + 1] = ae[h].y;
+    reduce_expanded<F>(aes, acc);
+  }
+  if constexpr (ROLL) {
     // the staged entries are used up: stage those of the row after the next (loads complete in order: before the leader's
     // request for the next row's iterate, which is the first thing the next row waits for)
     Tile::fetch(indices, data, opaque(lane), k0_nx2, end_nx2, col_nx, c_nx);
   }
+  return pAp;
 }
 
 // dynamic LDS of team_rows, in bytes: gramian [F][F], partial vectors [WAVES][F], operands [TEAMS][F], weight tables
@@ -356,6 +397,29 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
       }
     }
   };
+  // The last pass of a row hands in one float per wave (fused_pass, LAST), in the first word of the wave's partial slot.
+  auto arrive_scalar = [&](float v) {  // every wave
+    if constexpr (WPR > 1) {
+      if (lane == 0)
+        asm volatile("ds_write_b32 %0, %1\n\tds_add_u32 %2, %3" ::"v"(lds_off(parts + (size_t)wave * F)), "v"(v), "v"(arrivals_off), "v"(1u)
+                     : "memory");
+    }
+  };
+  auto collect_scalar = [&](float own) -> float {  // leader: wait for the team, sum its scalars in wave order
+    arr_target += WPR;
+    if constexpr (WPR > 1) {
+      while (poll(arrivals_off) < arr_target) __builtin_amdgcn_s_sleep(IMP_TEAM_NAP_LEADER);
+      asm volatile("" ::: "memory");  // the words below were written by inline assembly: no read of them moves above the wait
+      if constexpr (IMP_TEAM_LEADER_PRIO > 0) __builtin_amdgcn_s_setprio(IMP_TEAM_LEADER_PRIO);
+      const float *slot = parts + (size_t)(team * WPR) * F;  // uniform addresses: every lane reads the same WPR words
+      float sum = 0.f;
+#pragma unroll
+      for (int w = 0; w < WPR; ++w) sum += slot[(size_t)w * F];
+      return sum;
+    } else {
+      return own;
+    }
+  };
   auto operand_slot = [&]() { return reinterpret_cast<float *>(reinterpret_cast<char *>(vt) + cf4); };
   auto put_operand = [&](const float (&v)[FC]) {  // leader: compact -> natural order in the team's operand slot
     float *slot = operand_slot();
@@ -429,7 +493,7 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
     unsigned w = await_operand();
     {
       float acc[FC];
-      fused_pass<Tile, F, NJ, true, false>(y, cw, cnt, vt, j_begin, A0s, acc, lane, 0, ent_col, ent_c, Y, nullptr, nullptr, 0, 0);
+      fused_pass<Tile, F, NJ, true, false, false>(y, cw, cnt, vt, j_begin, A0s, acc, lane, 0, ent_col, ent_c, Y, nullptr, nullptr, 0, 0);
       arrive(acc);
     }
     if (leader) {
@@ -448,7 +512,7 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
     w = await_operand();
     for (int it = 0; (w & (kGo | kLast)) == kGo; ++it) {  // all steps but the last
       float acc[FC];
-      fused_pass<Tile, F, NJ, false, false>(y, cw, cnt, vt, j_begin, A0s, acc, lane, 0, ent_col, ent_c, Y, nullptr, nullptr, 0, 0);
+      fused_pass<Tile, F, NJ, false, false, false>(y, cw, cnt, vt, j_begin, A0s, acc, lane, 0, ent_col, ent_c, Y, nullptr, nullptr, 0, 0);
       arrive(acc);
       if (leader) {
         collect(Ap);
@@ -475,29 +539,31 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
     }
     // The last step stands outside the loop (the compiler must see that nothing of the row follows it): its pass rolls
     // the next row's tile in, and only its x update is evaluated -- the oracle's r, rsnew and p of the last step
-    // (_als.pyx:226-241) are never read again.
+    // (_als.pyx:226-241) are never read again, so neither is the vector A p: the pass hands back the wave's share of the
+    // scalar p . A p (fused_pass, LAST) and the leader sums WPR floats.
     const bool rolled = Tile::ROLL && (w & kGo) != 0u;
     if (w & kGo) {
-      float acc[FC];
+      float acc[FC], pAp;
       if constexpr (Tile::ROLL) {  // the tile of row i + i_step rolls in; the entries of row i + 2 i_step get staged
         int k2, cnt2;
         slice(b2, e2, k2, cnt2);
         if (i + i_step >= count) ent_cnt = 0;  // no next row (the schedule index is clamped): nothing to gather
-        fused_pass<Tile, F, NJ, false, true>(y, cw, cnt, vt, j_begin, A0s, acc, lane, ent_cnt, ent_col, ent_c, Y, indices, data, k2,
-                                             max(k2 + cnt2, b2 + 1));
+        pAp = fused_pass<Tile, F, NJ, false, true, true>(y, cw, cnt, vt, j_begin, A0s, acc, lane, ent_cnt, ent_col, ent_c, Y, indices,
+                                                         data, k2, max(k2 + cnt2, b2 + 1));
         cnt = ent_cnt;
         ent_cnt = cnt2;
         if (leader) load_compact<F>(X + (size_t)id1 * F, opaque(lane), x);  // the next row's iterate, into the carried registers
         else kill(x);
       } else {
         kill(x);
-        fused_pass<Tile, F, NJ, false, false>(y, cw, cnt, vt, j_begin, A0s, acc, lane, 0, ent_col, ent_c, Y, nullptr, nullptr, 0, 0);
+        pAp = fused_pass<Tile, F, NJ, false, true, false>(y, cw, cnt, vt, j_begin, A0s, acc, lane, 0, ent_col, ent_c, Y, nullptr,
+                                                          nullptr, 0, 0);
       }
-      arrive(acc);
+      arrive_scalar(pAp);
       if (leader) {
-        collect(Ap);
+        pAp = collect_scalar(pAp);
         get_operand(p);
-        const float alpha = rsold * __builtin_amdgcn_rcpf(dot_compact<F>(p, Ap));
+        const float alpha = rsold * __builtin_amdgcn_rcpf(pAp);
 #pragma unroll
         for (int cc = 0; cc < FC; ++cc) xc[cc] = fmaf(alpha, p[cc], xc[cc]);
         publish(0u);
