@@ -10,7 +10,9 @@
 
 namespace imp {
 
-__device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }  // (0,1)
+// (0, 1]: from 2^23 on, k + 0.5f is a tie that rounds to the even neighbour, and 16777215 + 0.5f rounds to 2^24 -- the 256 words
+// with their top 24 bits set give exactly 1.0 (uniform() then returns `high`, normal_kernel a zero radius: log(1) = 0, finite)
+__device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 __global__ void uniform_kernel(float *__restrict__ out, size_t n, uint64_t seed, uint32_t draw, float low, float high) {
   size_t quads = (n + 3) / 4;
