@@ -5,22 +5,22 @@
 // iterations, rsnew < 1e-20 break, empty rows zeroed.  It replaces the reference's CUDA launcher
 // and kernel (implicit/gpu/als.cu:23-111,154-197) behind LeastSquaresSolver::least_squares.
 //
-// MI355X mapping (not the reference's one-thread-per-factor block with a block reduction per nnz):
-//   * a 64-lane wavefront owns a row; lane l holds VPL consecutive factors of x, r, p, Ap in registers, so
-//     every gathered factor row Y[i,:] is ONE fully coalesced wave load (dwordx2 at f=128);
-//   * the nonzeros of a row are processed in TILES of T gathered rows held in registers: T partial dot
-//     products per lane are reduced with a butterfly REDUCE-SCATTER (v_permlane32_swap, v_permlane16_swap,
-//     then DPP row rotations) -- ~2.5 cross-lane instructions per dot instead of 7 -- the T weights are
-//     formed in the lanes that own them, broadcast with v_readlane and applied as T axpys;
-//   * rows with <= T nonzeros keep their gathered tile in registers across the 1+cg_steps passes, so
-//     their factor rows are read from memory exactly once (the roofline's single-pass traffic);
-//   * (YtY + reg I) is staged once per workgroup in LDS (64 KiB at f=128) and applied as a broadcast
-//     mat-vec: p_j from v_readlane, row j of the gramian from one conflict-free ds_read per lane;
-//   * rows are scheduled by length class (imp_csr::order): short (resident tile), mid (streamed
-//     tiles), and LONG rows (> kLongRow nnz) which are cut into segments: every CG pass becomes a
-//     segment-parallel partial kernel plus a per-row combine/update kernel, so a 150K-nnz row is
-//     spread over the whole chip instead of serialising one workgroup (fixed summation order).
-//   * any other f <= 512 runs a generic lane-strided variant of the same structure.
+// This file holds the entry point least_squares_cg, which picks one of three routes by factor count, and the kernels those routes
+// do not find in a file of their own:
+//   * f = 64 / 128, fp32 or fp16 storage (cg_f64_f128): long rows (> 512 nonzeros) through their explicit normal matrix on the
+//     matrix cores (als_cg_nm.hip), every other row on the quarter-layout register tiles of a wavefront or a team of wavefronts
+//     (als_cg_q*.hip);
+//   * f = 256 (cg_f256): long rows streamed, rows of 257 .. 512 nonzeros on als_cg_f256_kernel below -- one wavefront per row, the
+//     gramian staged through LDS in slices shared by the 8 rows of a workgroup -- and shorter rows resident in lock step
+//     (als_cg_w256.hip);
+//   * any other f <= 1024 (cg_generic): long rows streamed, every other row on als_cg_kernel below -- one wavefront per row, lane l
+//     holds factors l, l + 64, ... of x, r, p, Ap in registers, every gathered factor row is a coalesced wave load, four gathers in
+//     flight and one DPP all-reduce per dot product; (YtY + reg I) is staged once per workgroup in LDS where it fits (f < 192).
+//     By default only f > 256 gets here: every other f below 256 is zero-padded onto one of the first two routes (als_pad.hip).
+// Streamed long rows (launch_long): a row is cut into segments (imp_csr::plan_all); every CG pass is a segment-parallel partial
+// kernel plus a per-row combine / update kernel, so a 150K-nnz row is spread over the whole chip instead of serialising one
+// workgroup (fixed summation order).  The f = 64 / 128 route streams its long rows the same way under IMP_NM=0.
+// Rows are scheduled by length class (imp_csr::bin_start, common.h); empty rows are zeroed.
 #include <type_traits>
 
 #include "common.h"
@@ -81,7 +81,7 @@ __device__ __forceinline__ void sparse_pass(const int32_t *__restrict__ indices,
     sparse_pass_simple<VPL, VEC, FIRST>(indices, data, Y, f, lane, begin, end, vec, acc);
 }
 
-template <int VPL, bool VEC, int BLOCK, bool A_LDS>
+template <int VPL, int BLOCK, bool A_LDS>
 __device__ __forceinline__ const float *stage_gramian(float *smem, const float *__restrict__ A0, int f) {
   constexpr int LD = 64 * VPL;
   if constexpr (A_LDS) {
@@ -96,9 +96,8 @@ __device__ __forceinline__ const float *stage_gramian(float *smem, const float *
   }
 }
 
-// ---- fused kernel: one wavefront per row, rows [first, first+count) of the schedule -------------------------
-// RESIDENT: every row has <= T nonzeros and its gathered tile stays in registers across all passes.
-template <int VPL, bool VEC, int BLOCK, bool A_LDS, bool RESIDENT>
+// ---- generic kernel: one wavefront per row, rows [first, first+count) of the schedule, lane-strided factors -------------
+template <int VPL, int BLOCK, bool A_LDS>
 __global__ __launch_bounds__(BLOCK, (A_LDS && VPL == 2) ? 4 : 2) void als_cg_kernel(const int32_t *__restrict__ order, int first, int count,
                                                        const int32_t *__restrict__ indptr,
                                                        const int32_t *__restrict__ indices,
@@ -107,11 +106,11 @@ __global__ __launch_bounds__(BLOCK, (A_LDS && VPL == 2) ? 4 : 2) void als_cg_ker
                                                        int f, int cg_steps) {
   constexpr int LD = 64 * VPL;
   constexpr int WAVES = BLOCK / 64;
-  constexpr int T = tile_size<VPL>();
+  constexpr bool VEC = false;  // lane l holds factors l + 64 v
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const float *Amat = stage_gramian<VPL, VEC, BLOCK, A_LDS>(smem, A0, f);
+  const float *Amat = stage_gramian<VPL, BLOCK, A_LDS>(smem, A0, f);
   const int lda = A_LDS ? LD : f;
 
   for (int i = blockIdx.x * WAVES + wave; i < count; i += gridDim.x * WAVES) {
@@ -122,19 +121,13 @@ __global__ __launch_bounds__(BLOCK, (A_LDS && VPL == 2) ? 4 : 2) void als_cg_ker
     float x[VPL], r[VPL], p[VPL], Ap[VPL];
     load_row<VPL, VEC>(xrow, f, lane, x);
 
-    Tile<VPL, T> tile;
-    if constexpr (RESIDENT) load_tile<VPL, T>(tile, indices, data, Y, f, lane, row_begin, row_end);
-
     // r = -(A0 x) + sum_k (c+ - (|c|-1) y.x) y        (_als.pyx:187-201)
 #pragma unroll
     for (int v = 0; v < VPL; ++v) Ap[v] = 0.f;
     gram_matvec<VPL, VEC>(Amat, lda, lane, x, Ap, 0, f);
 #pragma unroll
     for (int v = 0; v < VPL; ++v) r[v] = -Ap[v];
-    if constexpr (RESIDENT)
-      tile_apply<VPL, T, true>(tile, lane, row_begin, row_end, x, r);
-    else
-      sparse_pass<VPL, VEC, true>(indices, data, Y, f, lane, row_begin, row_end, x, r);
+    sparse_pass<VPL, VEC, true>(indices, data, Y, f, lane, row_begin, row_end, x, r);
 
 #pragma unroll
     for (int v = 0; v < VPL; ++v) p[v] = r[v];
@@ -144,10 +137,7 @@ __global__ __launch_bounds__(BLOCK, (A_LDS && VPL == 2) ? 4 : 2) void als_cg_ker
 #pragma unroll
         for (int v = 0; v < VPL; ++v) Ap[v] = 0.f;
         gram_matvec<VPL, VEC>(Amat, lda, lane, p, Ap, 0, f);
-        if constexpr (RESIDENT)
-          tile_apply<VPL, T, false>(tile, lane, row_begin, row_end, p, Ap);
-        else
-          sparse_pass<VPL, VEC, false>(indices, data, Y, f, lane, row_begin, row_end, p, Ap);
+        sparse_pass<VPL, VEC, false>(indices, data, Y, f, lane, row_begin, row_end, p, Ap);
 
         float alpha = rsold / wave_allsum(dot_local<VPL>(p, Ap));
 #pragma unroll
@@ -402,7 +392,7 @@ __global__ __launch_bounds__(BLOCK) void cg_long_combine_kernel(const LongPlanDe
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const float *Amat = stage_gramian<VPL, VEC, BLOCK, A_LDS>(smem, A0, f);
+  const float *Amat = stage_gramian<VPL, BLOCK, A_LDS>(smem, A0, f);
   const int lda = A_LDS ? LD : f;
   const int vld = VEC ? LD : f;  // logical length for guarded loads from the LD-strided workspaces
   float *red = smem + (A_LDS ? (size_t)f * LD : 0);  // [WAVES][LD], ROWBLOCK only
@@ -554,14 +544,14 @@ template <typename T> static void zero_rows_t(const int32_t *order, int first, i
 }
 void zero_rows(const int32_t *order, int first, int count, float *X, int f) { zero_rows_t<float>(order, first, count, X, f); }
 
-template <int VPL, bool VEC, bool A_LDS, bool RESIDENT>
+template <int VPL, bool A_LDS>
 static void launch_fused(const imp_csr *C, int first, int count, float *X, const float *Y, const float *A0, int f,
                          int cg_steps, const char *name) {
   if (count <= 0) return;
   constexpr int BLOCK = 512;
   constexpr int LD = 64 * VPL;
   size_t lds = (A_LDS ? (size_t)f * LD : 0) * sizeof(float);
-  auto kern = als_cg_kernel<VPL, VEC, BLOCK, A_LDS, RESIDENT>;
+  auto kern = als_cg_kernel<VPL, BLOCK, A_LDS>;
   IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)std::max<size_t>(lds, 16)));
   int blocks_per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / BLOCK, (160 * 1024) / std::max<size_t>(lds, 1)));
@@ -634,151 +624,55 @@ static void launch_long(const imp_csr *C, const LongPlan &lp, T *X, const T *Y, 
   }
 }
 
-template <int VPL, bool VEC, bool A_LDS, typename T>
-static void launch_all(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int f, int cg_steps) {
-  // schedule classes (imp_csr): 0 long (segment-split), 1..4 mid, 5..6 short, 7 empty
-  const int32_t *b = C->bin_start;
-  if constexpr (VEC && A_LDS && (VPL == 1 || VPL == 2)) {
-    // f = 64 / 128: rows of more than 512 nonzeros through their explicit normal matrix on the matrix cores (als_cg_nm.hip).
-    // IMP_NM=0: one streamed pass per CG step instead (A/B, parity; the workgroup clusters of rounds 2-3 are gone)
-    if (nm_enabled()) least_squares_cg_nm<T>(C, X, Y, y_rows, A0, f, cg_steps);
-    else launch_long<VPL, VEC, A_LDS, T>(C, C->plan_all, X, Y, A0, f, cg_steps);
-    least_squares_cg_q<T>(C, X, Y, A0, f, cg_steps);  // quarter-layout register tiles, wave teams (als_cg_q.hip)
-  } else if constexpr (std::is_same<T, float>::value) {
-    launch_long<VPL, VEC, A_LDS, T>(C, C->plan_all, X, Y, A0, f, cg_steps);
-    if constexpr (VEC && VPL == 4 && !A_LDS) {  // f = 256: workgroup-shared gramian
-      if (w256_enabled()) {  // round 5: rows of <= 256 nonzeros resident, 16 / WPR rows per workgroup in lock step (als_cg_w256.hip)
-        launch_f256(C, b[1], b[2] - b[1], X, Y, A0, cg_steps, "als_cg_mid_rows");
-        least_squares_cg_w256(C, X, Y, A0, cg_steps);
-      } else {  // IMP_F256_OLD=1: every row streamed (A/B, parity)
-        launch_f256(C, b[1], b[7] - b[1], X, Y, A0, cg_steps, "als_cg_mid_rows");
-      }
-      zero_rows_t<T>(C->order.data(), C->first_empty(), C->n_empty(), X, f);
-      return;
-    }
-    bool resident_ok = false;
-    if constexpr (VEC) resident_ok = tile_size<VPL>() >= imp_csr::kShortRow;
-    if constexpr (VEC) {
-      if (resident_ok) {
-        launch_fused<VPL, VEC, A_LDS, false>(C, b[1], b[5] - b[1], X, Y, A0, f, cg_steps, "als_cg_mid_rows");
-        launch_fused<VPL, VEC, A_LDS, true>(C, b[5], b[7] - b[5], X, Y, A0, f, cg_steps, "als_cg_short_rows");
-      }
-    }
-    if (!resident_ok) launch_fused<VPL, VEC, A_LDS, false>(C, b[1], b[7] - b[1], X, Y, A0, f, cg_steps, "als_cg_mid_rows");
-  }
+// ---- the three routes.  Schedule classes (imp_csr): 0 long (segment-split), 1..4 mid, 5..6 short, 7 empty ------------------------
+// f = 64 VPL, VPL = 1 / 2, factors stored as fp32 or fp16
+template <int VPL, typename T>
+static void cg_f64_f128(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int cg_steps) {
+  constexpr int f = 64 * VPL;
+  // rows of more than 512 nonzeros through their explicit normal matrix on the matrix cores (als_cg_nm.hip).
+  // IMP_NM=0: one streamed pass per CG step instead (A/B, parity; the workgroup clusters of rounds 2-3 are gone)
+  if (solver_switches().nm) least_squares_cg_nm<T>(C, X, Y, y_rows, A0, f, cg_steps);
+  else launch_long<VPL, true, true, T>(C, C->plan_all, X, Y, A0, f, cg_steps);
+  least_squares_cg_q<T>(C, X, Y, A0, f, cg_steps);  // quarter-layout register tiles, wave teams (als_cg_q.hip)
   zero_rows_t<T>(C->order.data(), C->first_empty(), C->n_empty(), X, f);
+}
+
+// f = 256: workgroup-shared gramian
+static void cg_f256(const imp_csr *C, float *X, const float *Y, const float *A0, int cg_steps) {
+  constexpr int f = 256;
+  const int32_t *b = C->bin_start;
+  launch_long<4, true, false, float>(C, C->plan_all, X, Y, A0, f, cg_steps);
+  if (solver_switches().w256) {  // round 5: rows of <= 256 nonzeros resident, 16 / WPR rows per workgroup in lock step (als_cg_w256.hip)
+    launch_f256(C, b[1], b[2] - b[1], X, Y, A0, cg_steps, "als_cg_mid_rows");
+    least_squares_cg_w256(C, X, Y, A0, cg_steps);
+  } else {  // IMP_F256_OLD=1: every row streamed (A/B, parity)
+    launch_f256(C, b[1], b[7] - b[1], X, Y, A0, cg_steps, "als_cg_mid_rows");
+  }
+  zero_rows_t<float>(C->order.data(), C->first_empty(), C->n_empty(), X, f);
+}
+
+// any f <= 64 VPL on the lane-strided kernels
+template <int VPL, bool A_LDS>
+static void cg_generic(const imp_csr *C, float *X, const float *Y, const float *A0, int f, int cg_steps) {
+  const int32_t *b = C->bin_start;
+  launch_long<VPL, false, A_LDS, float>(C, C->plan_all, X, Y, A0, f, cg_steps);
+  launch_fused<VPL, A_LDS>(C, b[1], b[7] - b[1], X, Y, A0, f, cg_steps, "als_cg_mid_rows");
+  zero_rows_t<float>(C->order.data(), C->first_empty(), C->n_empty(), X, f);
 }
 
 // fp16 factor storage is handled natively (converted in registers) by the f = 64 / 128 kernels
 bool cg_native_half(int f) { return f == 64 || f == 128; }
 
-// ---- other factor counts below 128: zero-padded onto the f = 64 / 128 kernels ------------------------------------------------
-// The resident-tile kernels exist for f = 64 and 128.  Any other f < 128 (the reference's CPU default is 100) ran the generic
-// lane-strided one-wave-per-row kernel: 23.0 ms per configs[2]-shaped iteration at f = 100 against 4.6 at f = 128, 13-16 ms at
-// f = 16 / 32 / 50 against 2.7 at f = 64 (gpurun_out/r3s).  Padding is exact for CG: with the extra columns of X and Y zero and
-// the gramian extended by a unit diagonal block, residual, search direction and iterate stay zero in the padded components
-// (b = 0, x0 = 0 there), and every dot product only gains exact zeros.  Cost: one padded copy of Y and of the solved rows of X
-// in, the rows of X out -- (R_y + 2 R_x)(f + F) 4 bytes per half sweep, ~0.2 ms at configs[2] -- and the workspaces.
-__global__ void pad_rows_kernel(const float *__restrict__ src, float *__restrict__ dst, size_t rows, int f, int F,
-                                const int *__restrict__ skip = nullptr) {
-  if (skip && *skip) return;  // the padded copy is still the one this call needs (pad_check_kernel)
-  const size_t n = rows * (size_t)F;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / F;
-    const int c = (int)(i - r * F);
-    dst[i] = c < f ? src[r * f + c] : 0.f;
-  }
-}
-__global__ void unpad_rows_kernel(const float *__restrict__ src, float *__restrict__ dst, size_t rows, int f, int F) {
-  const size_t n = rows * (size_t)f;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / f;
-    dst[i] = src[r * F + (i - r * f)];
-  }
-}
-// *same = 1 iff the f x f gramian of this call equals, bit for bit, the top-left block of the padded gramian of the previous
-// one (single workgroup; the flag starts at 1 and any differing element clears it)
-__global__ void pad_check_kernel(const float *__restrict__ gram, const float *__restrict__ padded, int f, int F, int *same) {
-  if (threadIdx.x == 0) *same = 1;
-  __syncthreads();
-  bool differ = false;
-  for (int i = threadIdx.x; i < f * f; i += blockDim.x) {
-    const int r = i / f, c = i - r * f;
-    differ |= __float_as_uint(gram[i]) != __float_as_uint(padded[(size_t)r * F + c]);
-  }
-  if (differ) *same = 0;
-}
-__global__ void pad_gram_kernel(const float *__restrict__ src, float *__restrict__ dst, int f, int F) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < F * F; i += gridDim.x * blockDim.x) {
-    const int r = i / F, c = i - r * F;
-    dst[i] = (r < f && c < f) ? src[r * f + c] : (r == c ? 1.f : 0.f);
-  }
-}
-
+// Other factor counts below 256: zero-padded onto the f = 64 / 128 / 256 routes (als_pad.hip; exact for CG).  The generic kernel took
+// 23.0 ms per configs[2]-shaped iteration at f = 100 against 4.6 at f = 128, 13-16 ms at f = 16 / 32 / 50 against 2.7 at f = 64.
+// The padded copy of Y is kept for the next call against the same matrix (the row chunks of a sharded sweep).
 static void least_squares_cg_padded(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, int cg_steps, int F) {
-  const int f = (int)X->cols;
-  auto &c = ctx();
-  const size_t rx = (size_t)C->rows, ry = Y->rows;
-  if (c.pad_x.size < rx * F) c.pad_x.alloc(rx * F);
-  if (c.pad_y.size < ry * F) {
-    c.pad_y_src = nullptr;  // the old copy goes with its buffer (before the alloc: freeing it reports a write to that memory)
-    c.pad_y.alloc(ry * F);
-  }
-  if (c.pad_gram.size < (size_t)F * F) c.pad_gram.alloc((size_t)F * F);
-  auto grid = [&](size_t n) { return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)c.num_cus * 16)); };
-  {
-    IMP_PROF("pad_factors");
-    // The padded copy of Y is re-used when this call solves against the SAME matrix under the SAME gramian as the previous
-    // one -- the K row chunks of a sharded half sweep (4 redundant copies of a 10 M-row replica otherwise).  Same address, shape
-    // and factor counts are checked here; "same contents" is decided on the device, with no host wait, through the gramian:
-    // whoever changes Y recomputes YtY (the solve is meaningless otherwise), so a gramian equal bit for bit to the one the copy
-    // was made under vouches for it.  The flag is read by the pad kernel itself, which then returns at once.
-    const int *skip = nullptr;
-    if (ry && c.pad_y_src == Y->data && c.pad_y_rows == ry && c.pad_y_f == f && c.pad_y_F == F) {
-      if (c.pad_same.size < 1) c.pad_same.alloc(1);
-      pad_check_kernel<<<1, 1024, 0, stream()>>>(YtY->f32(), c.pad_gram.data(), f, F, c.pad_same.data());
-      skip = c.pad_same.data();
-    }
-    if (ry) pad_rows_kernel<<<grid(ry * F), 256, 0, stream()>>>(Y->f32(), c.pad_y.data(), ry, f, F, skip);
-    c.pad_y_src = Y->data, c.pad_y_rows = ry, c.pad_y_f = f, c.pad_y_F = F;
-    if (rx) pad_rows_kernel<<<grid(rx * F), 256, 0, stream()>>>(X->f32(), c.pad_x.data(), rx, f, F);
-    pad_gram_kernel<<<grid((size_t)F * F), 256, 0, stream()>>>(YtY->f32(), c.pad_gram.data(), f, F);
-    IMP_CHECK_HIP(hipGetLastError());
-  }
-  if (F == 64) launch_all<1, true, true, float>(C, c.pad_x.data(), c.pad_y.data(), ry, c.pad_gram.data(), F, cg_steps);
-  else if (F == 128) launch_all<2, true, true, float>(C, c.pad_x.data(), c.pad_y.data(), ry, c.pad_gram.data(), F, cg_steps);
-  else launch_all<4, true, false, float>(C, c.pad_x.data(), c.pad_y.data(), ry, c.pad_gram.data(), F, cg_steps);
-  {
-    IMP_PROF("unpad_factors");
-    if (rx) unpad_rows_kernel<<<grid(rx * f), 256, 0, stream()>>>(c.pad_x.data(), X->f32(), rx, f, F);
-    IMP_CHECK_HIP(hipGetLastError());
-  }
-}
-
-// The Cholesky entry's use of the same workspaces (als_cholesky.hip: 64 < f < 128 rides the f = 128 path): Y, the solved rows of X and the
-// gramian zero-padded to F columns, the gramian with a unit diagonal block -- the padded system is block diagonal, its solution the
-// original one followed by zeros.  The CG path's "same Y as last time" shortcut does not survive another user of pad_y.
-void cholesky_pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *YtY, size_t rx, int F) {
-  const int f = (int)X->cols;
-  auto &c = ctx();
-  const size_t ry = Y->rows;
-  if (c.pad_x.size < rx * F) c.pad_x.alloc(rx * F);
-  c.pad_y_src = nullptr;
-  if (c.pad_y.size < ry * F) c.pad_y.alloc(ry * F);
-  if (c.pad_gram.size < (size_t)F * F) c.pad_gram.alloc((size_t)F * F);
-  auto grid = [&](size_t n) { return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)c.num_cus * 16)); };
-  IMP_PROF("pad_factors");
-  if (ry) pad_rows_kernel<<<grid(ry * F), 256, 0, stream()>>>(Y->f32(), c.pad_y.data(), ry, f, F);
-  if (rx) pad_rows_kernel<<<grid(rx * F), 256, 0, stream()>>>(X->f32(), c.pad_x.data(), rx, f, F);
-  pad_gram_kernel<<<grid((size_t)F * F), 256, 0, stream()>>>(YtY->f32(), c.pad_gram.data(), f, F);
-  IMP_CHECK_HIP(hipGetLastError());
-}
-void cholesky_pad_out(imp_matrix *X, size_t rx, int F) {
-  auto &c = ctx();
-  auto grid = [&](size_t n) { return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)c.num_cus * 16)); };
-  IMP_PROF("unpad_factors");
-  if (rx) unpad_rows_kernel<<<grid(rx * X->cols), 256, 0, stream()>>>(c.pad_x.data(), X->f32(), rx, (int)X->cols, F);
-  IMP_CHECK_HIP(hipGetLastError());
+  const size_t rx = (size_t)C->rows;
+  const PaddedViews p = pad_in(X, Y, YtY, rx, F, true);
+  if (F == 64) cg_f64_f128<1, float>(C, p.X.f32(), p.Y.f32(), p.Y.rows, p.YtY.f32(), cg_steps);
+  else if (F == 128) cg_f64_f128<2, float>(C, p.X.f32(), p.Y.f32(), p.Y.rows, p.YtY.f32(), cg_steps);
+  else cg_f256(C, p.X.f32(), p.Y.f32(), p.YtY.f32(), cg_steps);
+  pad_out(X, rx, F);
 }
 
 void least_squares_cg(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, int cg_steps) {
@@ -791,29 +685,28 @@ void least_squares_cg(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, co
     if (!cg_native_half(f)) throw std::invalid_argument("least_squares: fp16 factors with this factor count are converted by the caller");
     __half *x = reinterpret_cast<__half *>(X->data);
     const __half *y = reinterpret_cast<const __half *>(Y->data);
-    if (f == 64) launch_all<1, true, true, __half>(C, x, y, Y->rows, a0, f, cg_steps);
-    else launch_all<2, true, true, __half>(C, x, y, Y->rows, a0, f, cg_steps);
+    if (f == 64) cg_f64_f128<1, __half>(C, x, y, Y->rows, a0, cg_steps);
+    else cg_f64_f128<2, __half>(C, x, y, Y->rows, a0, cg_steps);
     return;
   }
   float *x = X->f32();
   const float *y = Y->f32();
-  // IMP_NO_PAD=1: factor counts other than 64 / 128 on the generic kernels (A/B, parity)
-  static const bool no_pad = getenv("IMP_NO_PAD") != nullptr;
-  if (!no_pad && f < 256 && f != 64 && f != 128 && f >= 1) {  // 129 .. 255 (the reference publishes f = 192) ride the f = 256 kernels
+  // IMP_NO_PAD=1: factor counts other than 64 / 128 / 256 on the generic kernels (A/B, parity)
+  if (solver_switches().cg_pad && f < 256 && f != 64 && f != 128 && f >= 1) {  // 129 .. 255 (the reference publishes f = 192) ride the f = 256 kernels
     least_squares_cg_padded(C, X, YtY, Y, cg_steps, f < 64 ? 64 : (f < 128 ? 128 : 256));
     return;
   }
-  if (f == 64) launch_all<1, true, true, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f == 128) launch_all<2, true, true, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f == 256) launch_all<4, true, false, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f < 64) launch_all<1, false, true, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f < 128) launch_all<2, false, true, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f < 192) launch_all<3, false, true, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f < 256) launch_all<4, false, false, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f <= 384) launch_all<6, false, false, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f <= 512) launch_all<8, false, false, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f <= 768) launch_all<12, false, false, float>(C, x, y, Y->rows, a0, f, cg_steps);
-  else if (f <= 1024) launch_all<16, false, false, float>(C, x, y, Y->rows, a0, f, cg_steps);  // the reference's limit: one thread per factor, als.cu:177-179
+  if (f == 64) cg_f64_f128<1, float>(C, x, y, Y->rows, a0, cg_steps);
+  else if (f == 128) cg_f64_f128<2, float>(C, x, y, Y->rows, a0, cg_steps);
+  else if (f == 256) cg_f256(C, x, y, a0, cg_steps);
+  else if (f < 64) cg_generic<1, true>(C, x, y, a0, f, cg_steps);
+  else if (f < 128) cg_generic<2, true>(C, x, y, a0, f, cg_steps);
+  else if (f < 192) cg_generic<3, true>(C, x, y, a0, f, cg_steps);
+  else if (f < 256) cg_generic<4, false>(C, x, y, a0, f, cg_steps);
+  else if (f <= 384) cg_generic<6, false>(C, x, y, a0, f, cg_steps);
+  else if (f <= 512) cg_generic<8, false>(C, x, y, a0, f, cg_steps);
+  else if (f <= 768) cg_generic<12, false>(C, x, y, a0, f, cg_steps);
+  else if (f <= 1024) cg_generic<16, false>(C, x, y, a0, f, cg_steps);  // the reference's limit: one thread per factor, als.cu:177-179
   else throw std::invalid_argument("least_squares: factors must be <= 1024 (as the reference, implicit/gpu/als.cu:177-182)");
 }
 

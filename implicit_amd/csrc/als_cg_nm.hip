@@ -891,11 +891,6 @@ template <int F, typename T> void launch_nm(const imp_csr *C, T *X, const T *Y, 
 
 }  // namespace
 
-bool nm_enabled() {
-  static const bool on = !(getenv("IMP_NM") && atoi(getenv("IMP_NM")) == 0);
-  return on;
-}
-
 // Cholesky half sweep at f = 128 (round 5): every non-empty row's normal matrix on the matrix cores, factorised on its LDS image
 // (nm_chol).  Queues: the gramian image (reg on the diagonal), the long rows through the segment plan of the CG path (partial
 // images, their sum, the finishing kernel in Cholesky mode), every other row through als_chol_nm_rows_kernel.  Rows whose pivots

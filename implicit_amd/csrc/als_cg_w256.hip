@@ -577,11 +577,6 @@ void launch_w256_class(const imp_csr *C, int first, int count, float *X, const f
 
 }  // namespace
 
-bool w256_enabled() {
-  static const bool on = getenv("IMP_F256_OLD") == nullptr;
-  return on;
-}
-
 // rows of 1 .. 256 nonzeros (schedule classes 2 .. 6) of an f = 256 half sweep
 void least_squares_cg_w256(const imp_csr *C, float *X, const float *Y, const float *A0, int cg_steps) {
   const int32_t *b = C->bin_start;

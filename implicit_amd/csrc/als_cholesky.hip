@@ -719,83 +719,65 @@ __global__ __launch_bounds__(256, 3) void als_cholesky_f64_kernel(const int32_t 
 
 void zero_rows(const int32_t *order, int first, int count, float *X, int f);  // als_cg.hip
 
-// returns -1, or the smallest failing row
-int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg) {
-  const int f = (int)X->cols;
-  if (f > 1024) throw std::invalid_argument("least_squares_cholesky: factors must be <= 1024 (as the reference's GPU kernels, als.cu:177-182)");
-  // 64 < f < 128 (the reference's CPU default is 100): zero-padded onto the f = 128 path below -- Y and the gramian padded, the gramian
-  // with a unit diagonal block: the padded system is block diagonal and its solution the original one followed by zeros (its 4 x 4
-  // blocks factorise in the same order; the padded block rows never touch the others).  125 -> about 62 ms per configs[2]-shaped
-  // iteration at f = 100 against the workgroup kernel.  IMP_CHOL_PAD=0 (and the switches that ask for the workgroup kernels) keep it.
-  static const bool chol_pad = !(getenv("IMP_CHOL_PAD") && atoi(getenv("IMP_CHOL_PAD")) == 0) &&
-                               !(getenv("IMP_CHOL_NM") && atoi(getenv("IMP_CHOL_NM")) == 0);
-  // (not for a handful of rows against a large Y -- fold-in calls: the padded copy of Y would cost more than the solve)
-  if (f > 64 && f < 128 && chol_pad && C->nonempty() > 0 && (size_t)C->nnz * 4 >= Y->rows && X->itemsize == 4 && Y->itemsize == 4) {
-    constexpr int F = 128;
-    const size_t rx = (size_t)C->rows;
-    cholesky_pad_in(X, Y, YtY, rx, F);
-    auto &c = ctx();
-    imp_matrix Xp, Yp, Gp;
-    Xp.rows = rx, Xp.cols = F, Xp.data = c.pad_x.data();
-    Yp.rows = Y->rows, Yp.cols = F, Yp.data = c.pad_y.data();
-    Gp.rows = F, Gp.cols = F, Gp.data = c.pad_gram.data();
-    const int64_t failed = least_squares_cholesky(C, &Xp, &Gp, &Yp, reg);
-    cholesky_pad_out(X, rx, F);
-    sync();
-    return failed;
-  }
-  int lda = (f + 1) | 1;  // odd
-  // Packed rows of the augmented triangle (i (i + 1) / 2 + j): a must beyond f = 160, where the square image no longer fits the
-  // LDS, and a gain well below that -- at f = 128 the packed image lets THREE workgroups share a CU instead of two (measured
-  // 248 -> 174 ms per configs[2]-shaped iteration for one multiplication more per address)
-  const bool packed = f >= 96;
-  size_t lds = ((packed ? (size_t)(f + 1) * (f + 2) / 2 : (size_t)(f + 1) * lda) + (size_t)kCholTile * f + (size_t)kCholTile * (f + 1)) *
-               sizeof(float);
+// the device word the kernels atomicMin a failing row into, reset to "none"
+static unsigned long long *reset_failed_row() {
   auto &failb = ctx().chol_failed;
   if (failb.size < 1) failb.alloc(1);
-  unsigned long long *g_failed = failb.data();
-  IMP_CHECK_HIP(hipMemsetAsync(g_failed, 0xFF, sizeof(unsigned long long), stream()));
-  int nonempty = C->nonempty();
-  if (nonempty > 0 && f == 64) {
-    // every non-empty row: MFMA A-build + left-looking Cholesky, one wavefront per row
-    const size_t lds_m = ((size_t)64 * 68 + 4 * kCholTri) * sizeof(float);  // 52 KB: 3 workgroups per CU
-    // 159 VGPRs, 52 KB LDS: 3 workgroups per CU resident; 8x that many are launched -- smaller fixed shares of the length-sorted
-    // schedule, dealt by the hardware dispatcher as slots free up, even out the end of the launch (configs[1]: 14.8 -> 13.8 ms)
-    const int grid = std::min((nonempty + 3) / 4, ctx().num_cus * 3 * std::max(8, ctx().oversub));
-    // long rows: segment partials of the A-build first (see als_cholesky_f64_partial_kernel)
-    LongPlanDev plan = C->plan_chol.dev(C->order.data());
-    const float *partials = nullptr;
-    if (plan.n_seg > 0) {
-      auto &ws = ctx().long_ws;
-      const size_t need = (size_t)plan.n_seg * kCholPartial;
-      if (ws.size < need) ws.alloc(need);
-      partials = ws.data();
-      IMP_PROF("als_cholesky_long_partials");
-      const int pgrid = std::min((plan.n_seg + 3) / 4, ctx().num_cus * 8);
-      als_cholesky_f64_partial_kernel<<<pgrid, 256, 0, stream()>>>(plan, C->indices.data(), C->data.data(), Y->f32(), ws.data());
-      IMP_CHECK_HIP(hipGetLastError());
-    }
-    {
-      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(als_cholesky_f64_kernel<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
-      IMP_PROF("als_cholesky_mfma_rows");
-      als_cholesky_f64_kernel<false><<<grid, 256, lds_m, stream()>>>(C->order.data(), 0, nonempty, C->indptr.data(), C->indices.data(),
-                                                                     C->data.data(), X->f32(), Y->f32(), YtY->f32(), (float)reg,
-                                                                     g_failed, nullptr, plan, partials);
-      IMP_CHECK_HIP(hipGetLastError());
-    }
-    zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), f);
-    unsigned long long failed_m = 0;
-    IMP_CHECK_HIP(hipMemcpyAsync(&failed_m, g_failed, sizeof(failed_m), hipMemcpyDeviceToHost, stream()));
-    sync();
-    return failed_m == ~0ULL ? -1 : (int64_t)failed_m;
+  IMP_CHECK_HIP(hipMemsetAsync(failb.data(), 0xFF, sizeof(unsigned long long), stream()));
+  return failb.data();
+}
+// waits for the sweep; -1, or the smallest failing row
+static int64_t read_failed_row(const unsigned long long *g_failed) {
+  unsigned long long failed = 0;
+  IMP_CHECK_HIP(hipMemcpyAsync(&failed, g_failed, sizeof(failed), hipMemcpyDeviceToHost, stream()));
+  sync();
+  return failed == ~0ULL ? -1 : (int64_t)failed;
+}
+
+// f = 64: every non-empty row (there is one): MFMA A-build + left-looking Cholesky, one wavefront per row
+static int64_t cholesky_f64(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg) {
+  unsigned long long *g_failed = reset_failed_row();
+  const int nonempty = C->nonempty();
+  const size_t lds_m = ((size_t)64 * 68 + 4 * kCholTri) * sizeof(float);  // 52 KB: 3 workgroups per CU
+  // 159 VGPRs, 52 KB LDS: 3 workgroups per CU resident; 8x that many are launched -- smaller fixed shares of the length-sorted
+  // schedule, dealt by the hardware dispatcher as slots free up, even out the end of the launch (configs[1]: 14.8 -> 13.8 ms)
+  const int grid = std::min((nonempty + 3) / 4, ctx().num_cus * 3 * std::max(8, ctx().oversub));
+  // long rows: segment partials of the A-build first (see als_cholesky_f64_partial_kernel)
+  LongPlanDev plan = C->plan_chol.dev(C->order.data());
+  const float *partials = nullptr;
+  if (plan.n_seg > 0) {
+    auto &ws = ctx().long_ws;
+    const size_t need = (size_t)plan.n_seg * kCholPartial;
+    if (ws.size < need) ws.alloc(need);
+    partials = ws.data();
+    IMP_PROF("als_cholesky_long_partials");
+    const int pgrid = std::min((plan.n_seg + 3) / 4, ctx().num_cus * 8);
+    als_cholesky_f64_partial_kernel<<<pgrid, 256, 0, stream()>>>(plan, C->indices.data(), C->data.data(), Y->f32(), ws.data());
+    IMP_CHECK_HIP(hipGetLastError());
   }
+  {
+    IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(als_cholesky_f64_kernel<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
+    IMP_PROF("als_cholesky_mfma_rows");
+    als_cholesky_f64_kernel<false><<<grid, 256, lds_m, stream()>>>(C->order.data(), 0, nonempty, C->indptr.data(), C->indices.data(),
+                                                                   C->data.data(), X->f32(), Y->f32(), YtY->f32(), (float)reg,
+                                                                   g_failed, nullptr, plan, partials);
+    IMP_CHECK_HIP(hipGetLastError());
+  }
+  zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), 64);
+  return read_failed_row(g_failed);
+}
+
+// any other f: the normal-matrix path at f = 128, the wave kernels for the short rows at f <= 64, the workgroup kernel for the rest
+static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg) {
+  const int f = (int)X->cols;
+  unsigned long long *g_failed = reset_failed_row();
+  const int nonempty = C->nonempty();
   // f = 128 (round 5): the rows' normal matrices on the matrix cores, factorised on their LDS images (als_cg_nm.hip); the
   // workgroup kernel below then only takes the rows that path listed (non-positive or non-finite pivots: normally none).
   // IMP_CHOL_NM=0: every row on the workgroup kernel (A/B, parity)
-  static const bool chol_nm = !(getenv("IMP_CHOL_NM") && atoi(getenv("IMP_CHOL_NM")) == 0);
   CholNmList nm_list{nullptr, nullptr, 0};
-  const bool use_nm = f == 128 && chol_nm && nonempty > 0;
+  const bool use_nm = f == 128 && solver_switches().chol_nm && nonempty > 0;
   if (use_nm) nm_list = least_squares_cholesky_nm(C, X->f32(), Y->f32(), Y->rows, YtY->f32(), (float)reg);
   // other f <= 64: rows up to 256 nnz go to the register-resident wave kernel; longer rows (and any larger f) to the
   // workgroup kernel, whose 256 threads share the A-build of one row
@@ -804,27 +786,19 @@ int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix
   if (n_wave > 0) {
     int grid = std::min((n_wave + 3) / 4, ctx().num_cus * 8);
     IMP_PROF("als_cholesky_wave_rows");
-    if (f <= 32)
-      als_cholesky_wave_kernel<32><<<grid, 256, 0, stream()>>>(C->order.data(), n_block, n_wave, C->indptr.data(),
-                                                               C->indices.data(), C->data.data(), X->f32(), Y->f32(),
-                                                               YtY->f32(), f, (float)reg, g_failed);
-    else
-      als_cholesky_wave_kernel<64><<<grid, 256, 0, stream()>>>(C->order.data(), n_block, n_wave, C->indptr.data(),
-                                                               C->indices.data(), C->data.data(), X->f32(), Y->f32(),
-                                                               YtY->f32(), f, (float)reg, g_failed);
+    auto kern = f <= 32 ? als_cholesky_wave_kernel<32> : als_cholesky_wave_kernel<64>;
+    kern<<<grid, 256, 0, stream()>>>(C->order.data(), n_block, n_wave, C->indptr.data(), C->indices.data(), C->data.data(), X->f32(),
+                                     Y->f32(), YtY->f32(), f, (float)reg, g_failed);
     IMP_CHECK_HIP(hipGetLastError());
   }
   if (n_block > 0) {
-    {
-      const int m = f + 1, nbr = (m + 3) / 4, nbc = (f + 3) / 4;
-      const size_t a_words = packed ? (size_t)m * (m + 1) / 2 : (size_t)m * lda;
-      lds = (((a_words + 3) & ~(size_t)3) + (size_t)kCholTile * 4 * (nbc + nbr) + (size_t)m * kCholPanel + 4) * sizeof(float);
-    }
+    const int lda = (f + 1) | 1;  // odd
+    const int m = f + 1, nbr = (m + 3) / 4, nbc = (f + 3) / 4;
+    const size_t tiles = ((size_t)kCholTile * 4 * (nbc + nbr) + (size_t)m * kCholPanel + 4) * sizeof(float);  // staged tile, panel, flag
     if (f > 256) {
       // the triangle in a device workspace (als_cholesky_blocked_kernel<.., GLOBAL>): two workgroups per CU, a slice each
-      const int m = f + 1, nbr = (m + 3) / 4, nbc = (f + 3) / 4;
       const size_t a_words = ((size_t)m * lda + 3) & ~(size_t)3;
-      lds = ((size_t)kCholTile * 4 * (nbc + nbr) + (size_t)m * kCholPanel + 4) * sizeof(float);
+      const size_t lds = tiles;
       const int grid = std::min(n_block, ctx().num_cus * 2);
       auto &ws = ctx().long_ws;
       if (ws.size < a_words * (size_t)grid) ws.alloc(a_words * (size_t)grid);
@@ -835,8 +809,14 @@ int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix
                                          Y->f32(), YtY->f32(), f, (float)reg, lda, g_failed, 0, nullptr, ws.data());
       IMP_CHECK_HIP(hipGetLastError());
     } else {
-    int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
-      int grid = std::min(n_block, ctx().num_cus * per_cu * 4);  // smaller fixed shares of the length-sorted schedule
+      // Packed rows of the augmented triangle (i (i + 1) / 2 + j): a must beyond f = 160, where the square image no longer fits
+      // the LDS, and a gain well below that -- at f = 128 the packed image lets THREE workgroups share a CU instead of two
+      // (measured 248 -> 174 ms per configs[2]-shaped iteration for one multiplication more per address)
+      const bool packed = f >= 96;
+      const size_t a_words = packed ? (size_t)m * (m + 1) / 2 : (size_t)m * lda;
+      const size_t lds = ((a_words + 3) & ~(size_t)3) * sizeof(float) + tiles;
+      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
+      const int grid = std::min(n_block, ctx().num_cus * per_cu * 4);  // smaller fixed shares of the length-sorted schedule
       IMP_PROF("als_cholesky_rows");
       constexpr int ko = 0;  // (timing-only knock-outs of the phases: 1 A-build, 2 panel, 4 trailing update, 8 back substitution)
       auto kern = packed ? als_cholesky_blocked_kernel<true> : als_cholesky_blocked_kernel<false>;
@@ -852,10 +832,30 @@ int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix
     }
   }
   zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), f);
-  unsigned long long failed = 0;
-  IMP_CHECK_HIP(hipMemcpyAsync(&failed, g_failed, sizeof(failed), hipMemcpyDeviceToHost, stream()));
-  sync();
-  return failed == ~0ULL ? -1 : (int64_t)failed;
+  return read_failed_row(g_failed);
+}
+
+// returns -1, or the smallest failing row
+int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg) {
+  const int f = (int)X->cols;
+  if (f > 1024) throw std::invalid_argument("least_squares_cholesky: factors must be <= 1024 (as the reference's GPU kernels, als.cu:177-182)");
+  // 64 < f < 128 (the reference's CPU default is 100): zero-padded onto the f = 128 route (als_pad.hip; the 4 x 4 blocks of the padded
+  // system factorise in the same order, the padded block rows never touch the others).  125 -> about 62 ms per configs[2]-shaped
+  // iteration at f = 100 against the workgroup kernel.  IMP_CHOL_PAD=0 (and IMP_CHOL_NM=0, which asks for the workgroup kernels) keep it.
+  // Not for a handful of rows against a large Y -- fold-in calls: the padded copy of Y would cost more than the solve.  The copy is
+  // not kept: the CG route's "same Y as last time" shortcut does not survive another user of the workspace.
+  if (f > 64 && f < 128 && solver_switches().chol_pad && C->nonempty() > 0 && (size_t)C->nnz * 4 >= Y->rows && X->itemsize == 4 &&
+      Y->itemsize == 4) {
+    constexpr int F = 128;
+    const size_t rx = (size_t)C->rows;
+    PaddedViews p = pad_in(X, Y, YtY, rx, F, false);
+    const int64_t failed = cholesky_general(C, &p.X, &p.YtY, &p.Y, reg);
+    pad_out(X, rx, F);
+    sync();
+    return failed;
+  }
+  if (f == 64 && C->nonempty() > 0) return cholesky_f64(C, X, YtY, Y, reg);
+  return cholesky_general(C, X, YtY, Y, reg);
 }
 
 }  // namespace imp

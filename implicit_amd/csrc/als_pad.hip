@@ -1,0 +1,94 @@
+// Zero-padded systems: a half sweep at a factor count f that has no kernels of its own runs on those of a wider F.
+//
+// CG rides F = 64 / 128 / 256 for every other f < 256 (als_cg.hip), Cholesky F = 128 for 64 < f < 128 (als_cholesky.hip).  Y, the
+// solved rows of X and the gramian are copied with F columns, the new columns zero, the gramian extended by a unit diagonal
+// block.  The padded system is block diagonal: its solution is the original one followed by zeros.  For CG that is exact step by
+// step: residual, search direction and iterate stay zero in the padded components (b = 0, x0 = 0 there) and every dot product
+// only gains exact zeros.  Cost: one padded copy of Y and of the solved rows of X in, the rows of X out -- (R_y + 2 R_x)(f + F)
+// 4 bytes per half sweep, ~0.2 ms at configs[2] -- and the workspaces (PaddedSystem, common.h).
+#include "common.h"
+
+namespace imp {
+
+__global__ void pad_rows_kernel(const float *__restrict__ src, float *__restrict__ dst, size_t rows, int f, int F,
+                                const int *__restrict__ skip = nullptr) {
+  if (skip && *skip) return;  // the padded copy is still the one this call needs (pad_check_kernel)
+  const size_t n = rows * (size_t)F;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / F;
+    const int c = (int)(i - r * F);
+    dst[i] = c < f ? src[r * f + c] : 0.f;
+  }
+}
+__global__ void unpad_rows_kernel(const float *__restrict__ src, float *__restrict__ dst, size_t rows, int f, int F) {
+  const size_t n = rows * (size_t)f;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / f;
+    dst[i] = src[r * F + (i - r * f)];
+  }
+}
+// *same = 1 iff the f x f gramian of this call equals, bit for bit, the top-left block of the padded gramian of the previous
+// one (single workgroup; the flag starts at 1 and any differing element clears it)
+__global__ void pad_check_kernel(const float *__restrict__ gram, const float *__restrict__ padded, int f, int F, int *same) {
+  if (threadIdx.x == 0) *same = 1;
+  __syncthreads();
+  bool differ = false;
+  for (int i = threadIdx.x; i < f * f; i += blockDim.x) {
+    const int r = i / f, c = i - r * f;
+    differ |= __float_as_uint(gram[i]) != __float_as_uint(padded[(size_t)r * F + c]);
+  }
+  if (differ) *same = 0;
+}
+__global__ void pad_gram_kernel(const float *__restrict__ src, float *__restrict__ dst, int f, int F) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < F * F; i += gridDim.x * blockDim.x) {
+    const int r = i / F, c = i - r * F;
+    dst[i] = (r < f && c < f) ? src[r * f + c] : (r == c ? 1.f : 0.f);
+  }
+}
+
+static int pad_grid(size_t n) { return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)ctx().num_cus * 16)); }
+
+PaddedViews pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *YtY, size_t rows_of_X, int F, bool reuse_y) {
+  const int f = (int)X->cols;
+  PaddedSystem &p = ctx().pad;
+  const size_t rx = rows_of_X, ry = Y->rows;
+  if (p.x.size < rx * F) p.x.alloc(rx * F);
+  // a copy that may not be re-used, or that goes with its buffer, is forgotten (before the alloc: freeing the buffer reports a
+  // write to that memory)
+  if (!reuse_y || p.y.size < ry * F) p.forget_y();
+  if (p.y.size < ry * F) p.y.alloc(ry * F);
+  if (p.gram.size < (size_t)F * F) p.gram.alloc((size_t)F * F);
+  {
+    IMP_PROF("pad_factors");
+    // The padded copy of Y is re-used when this call solves against the SAME matrix under the SAME gramian as the previous
+    // one -- the K row chunks of a sharded half sweep (4 redundant copies of a 10 M-row replica otherwise).  Same address, shape
+    // and factor counts are checked here; "same contents" is decided on the device, with no host wait, through the gramian:
+    // whoever changes Y recomputes YtY (the solve is meaningless otherwise), so a gramian equal bit for bit to the one the copy
+    // was made under vouches for it.  The flag is read by the pad kernel itself, which then returns at once.
+    const int *skip = nullptr;
+    if (ry && p.y_src == Y->data && p.y_rows == ry && p.y_f == f && p.y_F == F) {
+      if (p.same.size < 1) p.same.alloc(1);
+      pad_check_kernel<<<1, 1024, 0, stream()>>>(YtY->f32(), p.gram.data(), f, F, p.same.data());
+      skip = p.same.data();
+    }
+    if (ry) pad_rows_kernel<<<pad_grid(ry * F), 256, 0, stream()>>>(Y->f32(), p.y.data(), ry, f, F, skip);
+    if (reuse_y) p.y_src = Y->data, p.y_rows = ry, p.y_f = f, p.y_F = F;
+    if (rx) pad_rows_kernel<<<pad_grid(rx * F), 256, 0, stream()>>>(X->f32(), p.x.data(), rx, f, F);
+    pad_gram_kernel<<<pad_grid((size_t)F * F), 256, 0, stream()>>>(YtY->f32(), p.gram.data(), f, F);
+    IMP_CHECK_HIP(hipGetLastError());
+  }
+  PaddedViews v;
+  v.X.rows = rx, v.X.cols = F, v.X.data = p.x.data();
+  v.Y.rows = ry, v.Y.cols = F, v.Y.data = p.y.data();
+  v.YtY.rows = F, v.YtY.cols = F, v.YtY.data = p.gram.data();
+  return v;
+}
+
+void pad_out(imp_matrix *X, size_t rows_of_X, int F) {
+  const int f = (int)X->cols;
+  IMP_PROF("unpad_factors");
+  if (rows_of_X) unpad_rows_kernel<<<pad_grid(rows_of_X * f), 256, 0, stream()>>>(ctx().pad.x.data(), X->f32(), rows_of_X, f, F);
+  IMP_CHECK_HIP(hipGetLastError());
+}
+
+}  // namespace imp

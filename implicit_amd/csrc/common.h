@@ -91,8 +91,16 @@ void sync();  // hipStreamSynchronize on the library stream
 // deferred mode (imp_set_deferred_sync), where the caller orders a whole iteration with ONE imp_device_synchronize
 void sync_call();
 unsigned long long *fixup_total();  // als_cg_fixup.hip: host-mapped count of the rows the fix-up kernel re-solved on this device
-bool w256_enabled();         // als_cg_w256.hip: resident lock-step kernels for the rows of <= 256 nonzeros at f = 256 (IMP_F256_OLD=1: round-2 kernel)
-bool nm_enabled();           // als_cg_nm.hip: long rows of the f = 64 / 128 path through their explicit normal matrix (IMP_NM=0: streamed)
+// The A/B and parity switches of the two ALS solvers, read from the environment once per process (containers.hip).  Every
+// route they select stays reachable: tests/test_gpu_solver_routes.py runs each of them.
+struct SolverSwitches {
+  bool nm;        // CG f = 64 / 128: long rows through their explicit normal matrix, als_cg_nm.hip (IMP_NM=0: streamed passes)
+  bool w256;      // CG f = 256: rows of <= 256 nonzeros on the resident lock-step kernels, als_cg_w256.hip (IMP_F256_OLD set: all streamed)
+  bool cg_pad;    // CG: other factor counts below 256 zero-padded onto f = 64 / 128 / 256 (IMP_NO_PAD set: the generic kernels)
+  bool chol_nm;   // Cholesky f = 128: normal matrices on the matrix cores, als_cg_nm.hip (IMP_CHOL_NM=0: the workgroup kernel)
+  bool chol_pad;  // Cholesky 64 < f < 128: zero-padded onto f = 128 (IMP_CHOL_PAD=0, or IMP_CHOL_NM=0: the workgroup kernel)
+};
+const SolverSwitches &solver_switches();
 
 // ---- launch-time profiler (HIP events on the library stream) ------------------------------------
 struct ProfScope {
@@ -140,6 +148,26 @@ template <typename T> struct DeviceArray {
   }
 };
 
+// Workspaces of a zero-padded half sweep (als_pad.hip): X, Y and the gramian with F >= f columns, and which matrix `y` is a
+// padded copy of -- the chunks of a sharded CG half sweep solve against the same Y, one padded copy serves them all.
+struct PaddedSystem {
+  DeviceArray<float> x, y, gram;
+  DeviceArray<int> same;  // device flag: the gramian of this call equals the one `y` was made under
+  const void *y_src = nullptr;
+  size_t y_rows = 0;
+  int y_f = 0, y_F = 0;
+  void forget_y() { y_src = nullptr; }
+  // the copy was made from memory that [dst, dst + bytes) overlaps
+  bool y_made_from(const void *dst, size_t bytes) const {
+    const char *a = static_cast<const char *>(dst), *b = static_cast<const char *>(y_src);
+    return b && a < b + y_rows * (size_t)y_f * sizeof(float) && b < a + bytes;
+  }
+  void release() {
+    x = {}, y = {}, gram = {};
+    forget_y();
+  }
+};
+
 // Scratch buffers are per DEVICE (a process may drive several devices through imp_set_device) and are only touched under
 // that device's call lock.
 struct Context {
@@ -165,13 +193,7 @@ struct Context {
   hipEvent_t pin_stage_ev = nullptr;
   DeviceArray<float> gram_ws;     // split-K partial gramians (gramian.hip)
   DeviceArray<float> long_ws;     // partial vectors / CG state of the long rows (als_cg.hip)
-  DeviceArray<float> pad_x, pad_y, pad_gram;  // zero-padded copies for factor counts that ride the f = 64 / 128 / 256 kernels (als_cg.hip)
-  // which matrix pad_y currently holds a padded copy of (als_cg.hip least_squares_cg_padded): the chunks of a sharded half sweep
-  // solve against the same Y, one padded copy serves them all
-  const void *pad_y_src = nullptr;
-  size_t pad_y_rows = 0;
-  int pad_y_f = 0, pad_y_F = 0;
-  DeviceArray<int> pad_same;  // device flag: the gramian of this call equals the one pad_y was made under
+  PaddedSystem pad;               // zero-padded copies for factor counts that ride the kernels of a wider one (als_pad.hip)
   DeviceArray<double> loss_buf;   // 4 accumulators of the loss kernel (solver.hip)
   DeviceArray<unsigned long long> chol_failed;  // smallest failing row of a Cholesky sweep (als_cholesky.hip)
   DeviceArray<float> barrier_word;              // operand of the RCCL barrier (comm.hip)
@@ -187,7 +209,7 @@ struct Context {
 };
 inline hipStream_t stream() { return ctx().stream; }
 // a C-ABI entry point is about to write `bytes` at `dst` through the library (or the memory is being freed): a padded copy of Y
-// made from memory it overlaps (least_squares_cg_padded) is no longer to be trusted -- on WHICHEVER device's context the copy
+// made from memory it overlaps (PaddedSystem) is no longer to be trusted -- on WHICHEVER device's context the copy
 // lives (device addresses are unique across the devices of a process; a Storage may die on a thread whose current device is
 // not the one that made the copy).  containers.hip.
 void note_device_write(const void *dst, size_t bytes);
@@ -301,11 +323,16 @@ struct imp_coo {
 };
 
 namespace imp {
+// als_pad.hip: the first rows_of_X rows of X, Y and the gramian zero-padded to F columns in ctx().pad (the gramian with a unit
+// diagonal block), as views; pad_out copies the solved rows back.  reuse_y: keep the copy of Y for the next call against the same
+// matrix under the same gramian (compared on the device) -- and use the one the previous call kept.
+struct PaddedViews {
+  imp_matrix X, Y, YtY;
+};
+PaddedViews pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *YtY, size_t rows_of_X, int F, bool reuse_y);
+void pad_out(imp_matrix *X, size_t rows_of_X, int F);
 // als_cg_nm.hip: Cholesky half sweep at f = 128 through the rows' normal matrices on the matrix cores; what it could not factorise
 // comes back as a device-side list for the workgroup-per-row fp32 kernel (als_cholesky.hip)
-// 64 < f < 128 Cholesky on the f = 128 path (als_cg.hip owns the pad kernels and workspaces)
-void cholesky_pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *YtY, size_t rx, int F);
-void cholesky_pad_out(imp_matrix *X, size_t rx, int F);
 struct CholNmList {
   const unsigned *count, *rows;
   int capacity;

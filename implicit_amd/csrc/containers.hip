@@ -59,11 +59,8 @@ void note_device_write(const void *dst, size_t bytes) {
     if (b && a < b + d->bytes && b < a + bytes) d->src = nullptr;
   }
   for (auto &kv : g_contexts) {
-    Context &c = *kv.second;
-    if (!c.pad_y_src) continue;
-    const char *b = static_cast<const char *>(c.pad_y_src);
-    const size_t b_bytes = c.pad_y_rows * (size_t)c.pad_y_f * sizeof(float);
-    if (a < b + b_bytes && b < a + bytes) c.pad_y_src = nullptr;
+    PaddedSystem &pad = kv.second->pad;
+    if (pad.y_made_from(dst, bytes)) pad.forget_y();
   }
 }
 
@@ -73,6 +70,24 @@ std::unique_lock<std::recursive_mutex> lock_device() {
   } catch (...) {
     return std::unique_lock<std::recursive_mutex>();  // no usable device: the body reports the error itself
   }
+}
+
+// "set to 0 turns it off": on unless the variable is set to a number that reads as zero
+static bool env_unless_zero(const char *name) {
+  const char *e = getenv(name);
+  return !(e && atoi(e) == 0);
+}
+const SolverSwitches &solver_switches() {
+  static const SolverSwitches s = [] {
+    SolverSwitches v;
+    v.nm = env_unless_zero("IMP_NM");
+    v.w256 = getenv("IMP_F256_OLD") == nullptr;
+    v.cg_pad = getenv("IMP_NO_PAD") == nullptr;
+    v.chol_nm = env_unless_zero("IMP_CHOL_NM");
+    v.chol_pad = v.chol_nm && env_unless_zero("IMP_CHOL_PAD");
+    return v;
+  }();
+  return s;
 }
 
 void sync() { IMP_CHECK_HIP(hipStreamSynchronize(stream())); }
@@ -420,10 +435,7 @@ int imp_release_workspaces(void) {
     // f = 100 to 128 is 5 GB): dropped here, re-allocated by the next call that needs them
     c.gram_ws = {};
     c.long_ws = {};
-    c.pad_x = {};
-    c.pad_y = {};
-    c.pad_y_src = nullptr;
-    c.pad_gram = {};
+    c.pad.release();
     c.nm_fix_rows = {};
     c.w256_ws = {};
     std::lock_guard<std::mutex> g(c.small_mutex);
