@@ -5,6 +5,8 @@
 // Arithmetic contract: the oracle's CG (implicit/cpu/_als.pyx:152-248).
 #include <type_traits>
 
+#include <algorithm>
+
 #include "als_qf_common.h"
 #include "common.h"
 
@@ -68,6 +70,91 @@ static void launch_qfteam(const imp_csr *C, int first, int count, T *X, const T 
                                       A0, cg_steps);
   IMP_CHECK_HIP(hipGetLastError());
 }
+
+// ---- the three 512-thread classes in one persistent launch ---------------------------------------------------------------
+// (128,256], (64,128] and (32,64] -- team widths 8, 4, 2 -- have the same workgroup shape and nearly the same LDS and register
+// needs.  As three launches each of them ends in a tail in which the device drains, and starts with a ramp in which every
+// workgroup stages the gramian again -- up to four times per slot inside a launch, which oversubscribed its grid to even its
+// fixed shares out.  Here the grid is exactly the resident workgroups; a workgroup stages the gramian once and runs the
+// classes in order, and inside a class its teams draw their rows by ticket (team_rows, TICKETS): the schedule is
+// longest-first, so tickets balance a class dynamically, and a workgroup that runs out of one class starts the next at
+// once.  No workgroup waits for another; the counters of the classes' queues are the only global state, and they are never
+// reset (team_tickets.h).  Every row's arithmetic is that of its class kernel, and no row depends on which team solves it, or when.
+struct ChainClassArgs {
+  int first[ChainTickets::kClasses], count[ChainTickets::kClasses];
+  unsigned base[ChainTickets::kClasses][ChainTickets::kQueues];
+};
+static_assert(ChainTickets::kQueues == kTicketQueues, "queues of a ticketed class");
+template <int F> constexpr size_t chain_lds_bytes() {
+  return std::max(team_lds_bytes<F, 8, 512, 32>(), std::max(team_lds_bytes<F, 4, 512, 32>(), team_lds_bytes<F, 2, 512, 32>()));
+}
+template <int F, typename ST>
+__global__ __launch_bounds__(512, F == 64 ? 8 : 4) void als_cg_qfteam_chain_kernel(const int32_t *__restrict__ order, ChainClassArgs cls,
+                                                                                  unsigned *__restrict__ counters,
+                                                                                  const int32_t *__restrict__ indptr,
+                                                                                  const int32_t *__restrict__ indices,
+                                                                                  const float *__restrict__ data, ST *__restrict__ X,
+                                                                                  const ST *__restrict__ Y, const float *__restrict__ A0,
+                                                                                  int cg_steps) {
+  static_assert(Tile32<ST>::T == 32, "chain_lds_bytes");
+  team_stage_gramian<F, 512>(A0);
+  bool entered = false;  // a class has run: its LDS layout is live until every wavefront of the workgroup has left it
+  static_for<ChainTickets::kClasses>([&](auto Cc) {
+    constexpr int C = decltype(Cc)::value, WPR = 8 >> C;
+    if (cls.count[C] > 0) {  // uniform over the grid
+      if (entered) __syncthreads();
+      entered = true;
+      team_rows<Tile32<ST>, F, WPR, 512, true, false>(order, cls.first[C], cls.count[C], indptr, indices, data, X, Y, A0, cg_steps,
+                                                      counters + (C * kTicketQueues + blockIdx.x % kTicketQueues) * ChainTickets::kCounterStride,
+                                                      cls.base[C][blockIdx.x % kTicketQueues]);
+    }
+  });
+}
+
+// workgroups per CU of a 512-thread team kernel with `lds` bytes of LDS (launch_qfteam)
+static int team512_per_cu(size_t lds) { return (int)std::max<size_t>(1, std::min<size_t>(2048 / 512, (160 * 1024) / lds)); }
+
+template <typename T>
+void launch_team_chain(const imp_csr *C, int f, const int (&first)[3], const int (&count)[3], T *X, const T *Y, const float *A0, int cg_steps,
+                       const char *name) {
+  if constexpr (std::is_same<T, float>::value) {
+    auto run = [&](auto Fc) {
+      constexpr int F = decltype(Fc)::value;
+      if (count[0] <= 0 && count[1] <= 0 && count[2] <= 0) return;
+      const size_t lds = chain_lds_bytes<F>();
+      auto kern = als_cg_qfteam_chain_kernel<F, T>;
+      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      // exactly the resident workgroups: tickets do what oversubscription did (and every queue needs a workgroup)
+      const int grid = std::max(ctx().num_cus * team512_per_cu(lds), ChainTickets::kQueues);
+      ChainClassArgs cls;
+      const int teams[3] = {1, 2, 4};  // per workgroup of 8 wavefronts
+      for (int c = 0; c < 3; ++c) {
+        if (count[c] >= ChainTickets::kMaxCount) throw std::invalid_argument("launch_team_chain: too many rows in a class");
+        cls.first[c] = first[c], cls.count[c] = std::max(count[c], 0);
+      }
+      Context &cx = ctx();
+      if (!cx.chain_counters.data())  // zeroed once, on the library stream
+        cx.chain_counters.alloc((size_t)ChainTickets::kClasses * ChainTickets::kQueues * ChainTickets::kCounterStride, true);
+      ChainTickets after = cx.chain_tickets;
+      after.launch(cls.count, grid, teams, cls.base);
+      IMP_PROF(name);
+      kern<<<grid, 512, lds, stream()>>>(C->order.data(), cls, cx.chain_counters.data(), C->indptr.data(), C->indices.data(),
+                                        C->data.data(), X, Y, A0, cg_steps);
+      IMP_CHECK_HIP(hipGetLastError());
+      cx.chain_tickets = after;  // a launch that was not queued draws nothing
+    };
+    // f = 64 keeps its per-class launches: its team kernels sit exactly at the 64 registers of 8 waves per SIMD, and the three
+    // row loops in one kernel do not fit (the chain compiles to 32 bytes of scratch per lane there; none at f = 128: 126 VGPRs)
+    if (f == 128) run(idx_t<128>{});
+    else throw std::invalid_argument("launch_team_chain: f must be 128");
+  } else {
+    throw std::invalid_argument("launch_team_chain: fp32 storage only (float16 storage runs its classes on the packed tiles)");
+  }
+}
+template void launch_team_chain<float>(const imp_csr *, int, const int (&)[3], const int (&)[3], float *, const float *, const float *, int,
+                                       const char *);
+template void launch_team_chain<__half>(const imp_csr *, int, const int (&)[3], const int (&)[3], __half *, const __half *, const float *,
+                                        int, const char *);
 
 // ---- short rows (<= 32 nnz) at f = 128: one wave per row, 16 rows per workgroup in lock step --------------------------------
 // The waves publish their operands in LDS; the dense part of a pass is ONE product A0 . P^T for the 16 rows, its 16-factor output

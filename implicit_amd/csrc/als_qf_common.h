@@ -111,6 +111,9 @@ template <int LANE> __device__ __forceinline__ float row_bcast_from(float v) {  
   return dpp_mov<0x150 + LANE>(v);
 }
 
+// queues of a ticketed row class (team_tickets.h ChainTickets::kQueues)
+constexpr int kTicketQueues = 8;
+
 // control word the leader publishes with every operand
 enum : unsigned { kGo = 1u, kLast = 2u };
 
@@ -303,14 +306,35 @@ template <int F, int WPR, int BLOCK, int T> constexpr size_t team_lds_bytes() {
   return ((size_t)F * F + WAVES * F + TEAMS * F + 2 * T * WAVES + 4 * TEAMS) * sizeof(float);
 }
 
-// Rows [first, first + count) of the schedule, a team of WPR wavefronts per row, up to T WPR nonzeros per row: the body of
-// als_cg_qfteam_kernel (Tile32) and als_cg_q64team_kernel (Tile64).
-template <typename Tile, int F, int WPR, int BLOCK, typename ST>
+// A team kernel has three parts: a workgroup prologue (the gramian image into LDS), a per-class set-up (the teams' control
+// words, one barrier) and the row loop.  A kernel of one row class runs them in sequence (team_rows with its defaults: the
+// body of als_cg_qfteam_kernel, Tile32, and als_cg_q64team_kernel, Tile64); the chain kernel of the three 512-thread classes
+// (als_cg_qfteam_chain_kernel, als_cg_qf.hip) runs the prologue once, here, and then set-up and row loop per class (STAGE false).
+template <int F, int BLOCK> __device__ __forceinline__ void team_stage_gramian(const float *__restrict__ A0) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  for (int e = threadIdx.x; e < F * F; e += BLOCK) smem[e] = A0[e];  // no barrier: the first class set-up has one
+}
+
+// One row class: rows [first, first + count) of the schedule, a team of WPR wavefronts per row, up to T WPR nonzeros per row
+// -- the (prologue,) set-up and the row loop.
+//   STAGE   false: the gramian image is in LDS already (at the start of the allocation, whatever the team width).
+//   TICKETS false: a team's rows are i = (blockIdx.x + k gridDim.x) TEAMS + team -- the per-class kernels.
+//   TICKETS true : a team draws its rows by ticket (team_tickets.h has the arithmetic).  The class is dealt to eight queues
+//     (one counter per queue; `counter` and `base` are those of this workgroup's): with N teams on a queue, team g starts
+//     with the tickets g, g + N, g + 2 N, g + 3 N -- the four rows the metadata pipeline holds -- and every later one is an
+//     atomic increment of *counter (tickets from 4 N on: counter - base + 4 N).  The leader draws at the top of a row,
+//     where nothing else of its wave is in flight, takes the value after the row's first pass and hands it to the team in
+//     the upper 30 bits of the row's STOP word -- the one control word of a row every wavefront reads last, on every path.
+//     No wavefront waits or polls for a ticket.  Tickets at or past the queue's end (clamped to it) behave like the clamped
+//     indices of the other mode; a team that holds one stops drawing.
+template <typename Tile, int F, int WPR, int BLOCK, bool TICKETS = false, bool STAGE = true, typename ST>
 __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int first, int count, const int32_t *__restrict__ indptr,
                                           const int32_t *__restrict__ indices, const float *__restrict__ data, ST *__restrict__ X,
-                                          const ST *__restrict__ Y, const float *__restrict__ A0, int cg_steps) {
+                                          const ST *__restrict__ Y, const float *__restrict__ A0, int cg_steps,
+                                          unsigned *counter = nullptr, unsigned base = 0u) {
   constexpr int FC = F / 64, FE = F / 16, T = Tile::T, WAVES = BLOCK / 64, TEAMS = WAVES / WPR, NJ = F / WPR / 4;
   static_assert(WPR <= WAVES && (F / WPR) % 4 == 0, "team width");
+  static_assert(!TICKETS || WPR > 1, "tickets travel in the team protocol");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *A0s = smem;                            // [F][F]
   float *parts = A0s + (size_t)F * F;           // [WAVES][F]  partial vectors of the waves (compact slots at their natural index)
@@ -321,9 +345,12 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int team = wave / WPR, sub = wave % WPR;
   const bool leader = sub == 0;
-  for (int e = threadIdx.x; e < F * F; e += BLOCK) A0s[e] = A0[e];
+  if constexpr (STAGE) {  // workgroup prologue (team_stage_gramian)
+    for (int e = threadIdx.x; e < F * F; e += BLOCK) A0s[e] = A0[e];
+  }
+  // per-class set-up: the control words start at zero
   if (threadIdx.x < 4 * TEAMS) ctl[threadIdx.x] = 0u;
-  __syncthreads();  // the only workgroup-wide barrier: from here on the teams run their rows independently
+  __syncthreads();  // the only workgroup-wide barrier of a class: from here on the teams run their rows independently
   const int j_begin = F * sub / WPR;
   float *vt = vts + (size_t)team * F;
   float *cw = cws + (size_t)wave * 2 * T;
@@ -436,9 +463,31 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
     }
   };
 
-  // this team's rows: i = (blockIdx.x + k gridDim.x) TEAMS + team; rows past the end re-read the last row
-  auto row_id = [&](int i) { return order[first + min(i, count - 1)]; };  // uniform address: scalar load
-  const int i_step = gridDim.x * TEAMS, i_first = blockIdx.x * TEAMS + team;
+  // this team's rows: i = (blockIdx.x + k gridDim.x) TEAMS + team, or its tickets; rows past the end re-read the last row
+  // TICKETS: the class is dealt to kTicketQueues queues, row k of the class to queue k mod 8, and the workgroups of queue q
+  // (blockIdx.x mod 8 = q: one XCD) share its rows; `rows`, the tickets and the team numbering are the queue's
+  const int queue = TICKETS ? (int)(blockIdx.x % kTicketQueues) : 0;
+  const int rows = TICKETS ? (count - queue + kTicketQueues - 1) / kTicketQueues : count;
+  auto row_id = [&](int i) {  // uniform address: scalar load
+    return order[first + min(TICKETS ? kTicketQueues * i + queue : i, count - 1)];
+  };
+  const int i_step = TICKETS ? (int)((gridDim.x - queue + kTicketQueues - 1) / kTicketQueues) * TEAMS : gridDim.x * TEAMS;
+  const int i_first = TICKETS ? (int)(blockIdx.x / kTicketQueues) * TEAMS + team : blockIdx.x * TEAMS + team;
+  // TICKETS: the tickets of the three rows after the one at the top of the body (the loop variable holds that one's), the
+  // ticket the leader has drawn for the team this row (clamped to `rows`), and the counter value of a draw on its way
+  int t1 = i_first + i_step, t2 = i_first + 2 * i_step, t3 = i_first + 3 * i_step;
+  unsigned drawn_ticket = (unsigned)rows, drawn = 0u;
+  // One global atomic from lane 0 of the leader, written out for the reason the LDS counters are (publish): the compiler's
+  // form counts lanes first.  Its result is waited for in take_draw, a pass later; until then the compiler knows of no load
+  // in flight, and a wait it places for loads of its own can only wait longer for it.
+  auto draw = [&]() {
+    if (lane == 0) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(drawn) : "v"(counter), "v"(1u) : "memory");
+  };
+  auto take_draw = [&]() {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(drawn)::"memory");
+    drawn_ticket = min((unsigned)__builtin_amdgcn_readfirstlane(drawn) - base + 4u * (unsigned)i_step, (unsigned)rows);
+  };
+  auto stop_word = [&]() -> unsigned { return TICKETS ? drawn_ticket << 2 : 0u; };  // leader: go and last clear
   auto slice = [&](int rb, int re, int &k0, int &cnt) {  // even shares rounded up to whole 4-entry tile steps
     const int chunk = min(T, (((re - rb) + WPR - 1) / WPR + 3) & ~3);
     k0 = min(rb + chunk * sub, re);
@@ -464,7 +513,7 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
   typename Tile::elem y[T / 4][FE / 2];  // the resident tile
   float x[FC];  // x: the leader's loop-carried iterate registers (the last step loads the NEXT row's into them)
   kill(x);
-  for (int i = i_first; i < count; i += i_step) {
+  for (int i = i_first; i < rows; i += TICKETS ? 0 : i_step) {
     ST *xrow = X + (size_t)id0 * F;
     if (!tile_ready) {  // first row of the wave, or the previous row ended before its last pass: plain row start
       cnt = ent_cnt;
@@ -489,6 +538,9 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
 #pragma unroll
       for (int cc = 0; cc < FC; ++cc) xc[cc] = x[cc];  // this row's iterate moves on as xc; x is re-loaded for the next row
       publish(kGo);
+      if constexpr (TICKETS) {
+        if (t3 < rows) draw();  // the ticket that follows t3; a team whose newest ticket is past the end draws no more
+      }
     }
     unsigned w = await_operand();
     {
@@ -502,11 +554,14 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
       for (int cc = 0; cc < FC; ++cc) r[cc] = -r[cc], p[cc] = r[cc];
       rsold = dot_compact<F>(r, r);
       store = rsold >= 1e-20f;  // else: x untouched (_als.pyx:206)
+      if constexpr (TICKETS) {
+        if (t3 < rows) take_draw();
+      }
       if (store && cg_steps > 0) {
         put_operand(p);
         publish(kGo | (cg_steps == 1 ? kLast : 0u));
       } else {
-        publish(0u);
+        publish(stop_word());
       }
     }
     w = await_operand();
@@ -525,7 +580,7 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
         }
         const float rsnew = dot_compact<F>(r, r);
         if (rsnew < 1e-20f) {
-          publish(0u);  // the oracle breaks here (_als.pyx:235)
+          publish(stop_word());  // the oracle breaks here (_als.pyx:235)
         } else {
           const float beta = rsnew * __builtin_amdgcn_rcpf(rsold);
 #pragma unroll
@@ -547,7 +602,7 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
       if constexpr (Tile::ROLL) {  // the tile of row i + i_step rolls in; the entries of row i + 2 i_step get staged
         int k2, cnt2;
         slice(b2, e2, k2, cnt2);
-        if (i + i_step >= count) ent_cnt = 0;  // no next row (the schedule index is clamped): nothing to gather
+        if ((TICKETS ? t1 : i + i_step) >= rows) ent_cnt = 0;  // no next row (the schedule index is clamped): nothing to gather
         pAp = fused_pass<Tile, F, NJ, false, true, true>(y, cw, cnt, vt, j_begin, A0s, acc, lane, ent_cnt, ent_col, ent_c, Y, indices,
                                                          data, k2, max(k2 + cnt2, b2 + 1));
         cnt = ent_cnt;
@@ -566,15 +621,23 @@ __device__ __forceinline__ void team_rows(const int32_t *__restrict__ order, int
         const float alpha = rsold * __builtin_amdgcn_rcpf(pAp);
 #pragma unroll
         for (int cc = 0; cc < FC; ++cc) xc[cc] = fmaf(alpha, p[cc], xc[cc]);
-        publish(0u);
+        publish(stop_word());
       }
-      (void)await_operand();  // the stop generation: keeps every wave's count in step with the leader's
+      // the stop generation: keeps every wave's count in step with the leader's
+      if constexpr (TICKETS) w = await_operand();
+      else (void)await_operand();
     } else {
       kill(x);
     }
     if (leader && store) store_compact<F>(xrow, opaque(lane), xc);
     tile_ready = rolled;
-    id0 = id1, id1 = id2, id2 = id3, id3 = row_id(i + 4 * i_step);
+    if constexpr (TICKETS) {
+      // on every path `w` is now the row's stop word: the same ticket in every wavefront of the team
+      i = t1, t1 = t2, t2 = t3, t3 = (int)(w >> 2);
+      id0 = id1, id1 = id2, id2 = id3, id3 = row_id(t3);
+    } else {
+      id0 = id1, id1 = id2, id2 = id3, id3 = row_id(i + 4 * i_step);
+    }
     b0 = b1, e0 = e1, b1 = b2, e1 = e2, b2 = indptr[id2], e2 = indptr[id2 + 1];
   }
 }

@@ -15,6 +15,7 @@
 
 #include "../../include/implicit_hip.h"
 #include "csr_schedule.h"
+#include "team_tickets.h"
 
 namespace imp {
 
@@ -110,6 +111,7 @@ struct ProfScope {
   hipEvent_t start = nullptr, stop = nullptr;
 };
 bool prof_enabled();
+bool prof_unfiltered();  // on, and with no name filter: every scope is timed (a per-kernel pass such as bench.py --full's)
 #define IMP_PROF(name) ::imp::ProfScope _prof_scope_(name)
 
 // ---- device storage ---------------------------------------------------------------------------
@@ -200,6 +202,8 @@ struct Context {
   unsigned long long *fixup_total = nullptr;     // host-mapped: rows re-solved by the fp32 fix-up kernel since the last imp_solver_fixup_rows(reset)
   DeviceArray<float> w256_ws;                    // fp16-split gramian in fragment order + header (als_cg_w256.hip)
   DeviceArray<unsigned> nm_fix_rows;             // rows the normal-matrix kernels left to the fix-up kernel (operands beyond the fp16 range)
+  DeviceArray<unsigned> chain_counters;          // ticket counters of the chained mid-row classes, zeroed once and never reset (als_cg_qf.hip)
+  ChainTickets chain_tickets;                    // what those counters read after everything queued so far (team_tickets.h)
   DeviceArray<int> nm_ticket;                    // work counter of the normal-matrix kernel (als_cg_nm.hip), reset by every launch
   DeviceArray<unsigned long long> bpr_stats;     // correct / skipped counts and the id check's violation bits of bpr_update (bpr.hip)
   DeviceArray<float> lmf_ws;                     // partial sums of the long rows' segments of lmf_update (lmf.hip)

@@ -112,6 +112,10 @@ static std::vector<ProfPending> g_prof_pending;
 static std::vector<hipEvent_t> g_event_pool;
 
 bool prof_enabled() { return g_prof_on; }
+bool prof_unfiltered() {
+  std::lock_guard<std::recursive_mutex> plock(g_prof_mutex);
+  return g_prof_on && g_prof_filter.empty();
+}
 
 static hipEvent_t get_event() {
   if (!g_event_pool.empty()) {
@@ -573,6 +577,32 @@ int imp_host_csr_plan(int32_t rows, int32_t cols, const int32_t *indptr, const i
     std::copy(p.xcd_start, p.xcd_start + 9, xcd_start);
     const int32_t fields[8] = {p.n_long, p.n_seg, p.striped, s.n_chol_long, s.nm_segment, s.nm_multi_rows, s.nm_multi_segs, 0};
     std::copy(fields, fields + 8, info);
+  });
+}
+
+// ---- host-side helper: the ticket bases of the chained mid-row launch (team_tickets.h) ----------------
+// One launch of the bookkeeping launch_team_chain keeps per device, on a state the caller owns: next[3][8] is advanced in
+// place, base[3][8] and draws[3][8] are what the launch is told and how many tickets it draws per queue.
+int imp_host_chain_tickets(uint32_t *next, const int32_t *count, int32_t workgroups, const int32_t *teams_per_workgroup, uint32_t *base,
+                           uint32_t *draws) {
+  return guarded_host([&] {
+    constexpr int NC = ChainTickets::kClasses, NQ = ChainTickets::kQueues;
+    ChainTickets t;
+    int32_t c[NC], n[NC];
+    uint32_t b[NC][NQ];
+    if (workgroups <= 0) throw std::invalid_argument("host_chain_tickets: the grid holds at least one workgroup");
+    for (int k = 0; k < NC; ++k) {
+      if (count[k] < 0 || count[k] >= ChainTickets::kMaxCount || teams_per_workgroup[k] <= 0)
+        throw std::invalid_argument("host_chain_tickets: a class holds 0 .. 2^30 - 1 rows and a workgroup at least one team");
+      c[k] = count[k], n[k] = teams_per_workgroup[k];
+      for (int q = 0; q < NQ; ++q) t.next[k][q] = next[k * NQ + q];
+    }
+    t.launch(c, workgroups, n, b);
+    for (int k = 0; k < NC; ++k)
+      for (int q = 0; q < NQ; ++q) {
+        draws[k * NQ + q] = t.next[k][q] - next[k * NQ + q];
+        next[k * NQ + q] = t.next[k][q], base[k * NQ + q] = b[k][q];
+      }
   });
 }
 

@@ -128,3 +128,19 @@ def csr_schedule(m, which=0, segment=512, stripe=-1, nm_segment=0, num_cus=256):
     out["row_seg"] = out["row_seg"][:out["n_long"] + 1]
     out.update({k: v[:out["n_seg"]] for k, v in segs.items()})
     return out
+
+
+def chain_tickets(state, counts, workgroups, teams_per_workgroup=(1, 2, 4)):
+    """One launch of the ticket bookkeeping of the chained mid-row CG classes (imp_host_chain_tickets, host code): `state`, a
+    uint32 array [3, 8] of the counter values of the classes' queues, is advanced in place; returns (base, draws) of the
+    launch, [3, 8] each, for the row counts per class, the workgroups of the grid and the teams of each class in one."""
+    from .gpu._hip import check, lib
+
+    assert state.dtype == np.uint32 and state.shape == (3, 8) and state.flags.c_contiguous
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    teams = np.ascontiguousarray(teams_per_workgroup, dtype=np.int32)
+    assert counts.shape == teams.shape == (3,)
+    base, draws = np.empty((3, 8), np.uint32), np.empty((3, 8), np.uint32)
+    check(lib().imp_host_chain_tickets(state.ctypes.data, counts.ctypes.data, int(workgroups), teams.ctypes.data, base.ctypes.data,
+                                       draws.ctypes.data))
+    return base, draws

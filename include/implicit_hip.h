@@ -106,6 +106,14 @@ int imp_host_csr_plan(int32_t rows, int32_t cols, const int32_t *indptr, const i
                       int64_t seg_capacity, int32_t *seg_row, int32_t *seg_begin, int32_t *seg_end, int32_t *seg_exec,
                       int32_t *xcd_start, int32_t *info);
 
+/* Host code, no device involved: one launch of the ticket bookkeeping of the chained mid-row CG classes (team widths 8, 4, 2,
+ * eight queues each; csrc/team_tickets.h) on a state the caller owns.  next[3][8]: the values the queues' device counters read
+ * before the launch, advanced in place (modulo 2^32) by the tickets the launch draws; count[3]: rows per class (0 .. 2^30 - 1);
+ * workgroups: the grid (> 0); teams_per_workgroup[3] (> 0).  Outputs: base[3][8], the counter values the kernel is told, and
+ * draws[3][8]. */
+int imp_host_chain_tickets(uint32_t *next, const int32_t *count, int32_t workgroups, const int32_t *teams_per_workgroup, uint32_t *base,
+                           uint32_t *draws);
+
 /* ---- Matrix (matrix.h:23-90, matrix.cu:34-220) -------------------------------------------- */
 /* Matrix(rows, cols, data, allocate=true, itemsize): allocates; copies rows*cols*itemsize bytes
  * from host_data when non-NULL, zero-fills otherwise (matrix.cu:80-96). */
