@@ -468,6 +468,91 @@ def sparse_topk_product(A, B, k, zero_own_columns=False):
     return ids, scores, counts
 
 
+def _eval_pattern(test_user_items, k):
+    """The arguments imp_eval_create and imp_host_ranking_metrics share: the held-out CSR pattern (rows strictly increasing:
+    sorted, duplicates merged) and the two discount tables of length k (evaluation.pyx:408-409)."""
+    k = int(k)
+    if not 1 <= k < 2**31:
+        raise ValueError("ranking metrics: K must be >= 1")
+    rows, cols = (int(d) for d in test_user_items.shape)
+    if max(rows, cols) > np.iinfo(np.int32).max:
+        raise ValueError("ranking metrics: dimensions must fit int32")
+    indptr = np.ascontiguousarray(test_user_items.indptr)
+    if indptr.dtype not in (np.int32, np.int64):
+        indptr = indptr.astype(np.int64)
+    indices = np.asarray(test_user_items.indices)
+    if indices.dtype != np.int32:
+        if len(indices) and (indices.max() > np.iinfo(np.int32).max or indices.min() < 0):
+            raise ValueError("ranking metrics: column index out of range")
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    cg = 1.0 / np.log2(np.arange(2, k + 2))
+    cg_sum = np.cumsum(cg)
+    return rows, cols, indptr, int(indptr.dtype == np.int64), indices, k, cg, cg_sum
+
+
+_SUM_NAMES = ("relevant", "pr_div", "sum_ap", "sum_ndcg", "sum_auc", "total")
+
+
+class RankingMetrics:
+    """NEW: running sums of P@K / MAP@K / NDCG@K / AUC@K over recommendation rows that stay on the device (imp_eval,
+    csrc/evaluation.hip; the reference computes them in a host loop, evaluation.pyx:437-466).  `test_user_items`: the
+    held-out scipy CSR matrix in canonical form (sorted rows, no duplicates; ValueError otherwise); only its pattern is
+    read, every stored entry is a like."""
+
+    def __init__(self, test_user_items, K):
+        rows, cols, indptr, is64, indices, k, cg, cg_sum = _eval_pattern(test_user_items, K)
+        self.K, self.shape = k, (rows, cols)
+        self._h = ctypes.c_void_p()
+        check(lib().imp_eval_create(rows, cols, _vp(indptr), is64, _vp(indices), k, _vp(cg), _vp(cg_sum), ctypes.byref(self._h)))
+
+    def add(self, ids, userids, per_row=False):
+        """ids: the n x K device Matrix KnnQuery.topk_device returns (int32 bit patterns), or a host int32 array (uploaded);
+        userids: the n rows of the test matrix they belong to (IntVector or int32 array).  Users with nothing held out, or
+        outside the matrix, add nothing.  Only queues work, unless per_row is set: then returns an n x 4 float64 array of
+        each row's (hits, ap, ndcg, auc) terms."""
+        if not isinstance(ids, Matrix):
+            ids = np.ascontiguousarray(ids)
+            if ids.dtype != np.int32 or ids.ndim != 2:
+                raise ValueError("RankingMetrics.add expects a 2-d int32 array of ids")
+            ids = Matrix(ids.view(np.float32))  # the bits travel untouched
+        if not isinstance(userids, IntVector):
+            userids = IntVector(np.ascontiguousarray(userids, dtype=np.int32))
+        out = np.empty((userids.size, 4), dtype=np.float64) if per_row else None
+        check(lib().imp_eval_add(self._h, ids._h, userids._h, _vp(out) if per_row else None))
+        return out
+
+    def sums(self):
+        """Waits for the queued work; {relevant, pr_div, sum_ap, sum_ndcg, sum_auc, total} as floats."""
+        out = np.zeros(6, dtype=np.float64)
+        check(lib().imp_eval_result(self._h, _vp(out)))
+        return dict(zip(_SUM_NAMES, out.tolist()))
+
+    def reset(self):
+        check(lib().imp_eval_reset(self._h))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().imp_eval_destroy(self._h)
+            self._h = None
+
+
+def host_ranking_metrics(test_user_items, K, ids, userids, per_row=False):
+    """NEW: the sums of RankingMetrics for host ids (n x K int32) in plain host code (imp_host_ranking_metrics; no device
+    involved).  Returns the dict of six sums, and with per_row also the n x 4 array of (hits, ap, ndcg, auc) terms.  A
+    non-canonical test matrix raises ValueError, a user id outside it IndexError."""
+    rows, cols, indptr, is64, indices, k, cg, cg_sum = _eval_pattern(test_user_items, K)
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    userids = np.ascontiguousarray(userids, dtype=np.int32)
+    if ids.ndim != 2 or ids.shape != (len(userids), k):
+        raise ValueError("host_ranking_metrics: ids must have one row of K ids per user id")
+    sums = np.zeros(6, dtype=np.float64)
+    out = np.empty((len(userids), 4), dtype=np.float64) if per_row else None
+    check(lib().imp_host_ranking_metrics(rows, cols, _vp(indptr), is64, _vp(indices), k, _vp(cg), _vp(cg_sum), _vp(ids),
+                                         _vp(userids), len(userids), _vp(sums), _vp(out) if per_row else None))
+    sums = dict(zip(_SUM_NAMES, sums.tolist()))
+    return (sums, out) if per_row else sums
+
+
 class Comm:
     """NEW: RCCL communicator, one process per GPU (include/implicit_hip.h, imp_comm_*)."""
 

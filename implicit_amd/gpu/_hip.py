@@ -97,6 +97,15 @@ _SIGNATURES = {
     "imp_spmat_destroy": [ctypes.c_void_p],
     "imp_sparse_topk_product": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p],
+    "imp_eval_create": [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                        ctypes.c_void_p, ctypes.c_void_p, c_void_pp],
+    "imp_eval_add": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    "imp_eval_result": [ctypes.c_void_p, ctypes.c_void_p],
+    "imp_eval_reset": [ctypes.c_void_p],
+    "imp_eval_destroy": [ctypes.c_void_p],
+    "imp_host_ranking_metrics": [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                 ctypes.c_void_p, ctypes.c_void_p],
     "imp_comm_unique_id": [ctypes.c_void_p],
     "imp_comm_init_rank": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_void_pp],
     "imp_comm_destroy": [ctypes.c_void_p],

@@ -40,16 +40,7 @@ class MatrixFactorizationBase(RecommenderBase):
             if user_items.shape[0] != (1 if scalar else len(userid)):
                 raise ValueError("user_items must contain 1 row for every user in userids")
 
-        if recalculate_user:
-            query = self.recalculate_user(userid, user_items)
-        elif not scalar and len(userid) > 1 and isinstance(userid, np.ndarray) and userid.dtype.kind in "iu" and \
-                userid[0] >= 0 and userid[-1] - userid[0] == len(userid) - 1 and (np.diff(userid) == 1).all():
-            # a run of consecutive ids (what batched callers pass): a row-range VIEW of the factors, no gather
-            if userid[-1] >= self.user_factors.shape[0]:
-                raise IndexError("row id out of range for selecting items from matrix")
-            query = self.user_factors[int(userid[0]):int(userid[-1]) + 1]
-        else:
-            query = self.user_factors[userid]
+        query = self.recalculate_user(userid, user_items) if recalculate_user else self._user_query(userid)
 
         candidates = self.item_factors
         if items is not None:
@@ -68,8 +59,7 @@ class MatrixFactorizationBase(RecommenderBase):
         query_filter = None
         if filter_already_liked_items:
             liked = user_items if items is None else _filter_items_from_sparse_matrix(items, user_items)
-            if liked.nnz:
-                query_filter = gpu.COOMatrix.from_csr_pattern(liked)  # the filter reads (row, col) only
+            query_filter = self._liked_filter(liked)
 
         ids, scores = self.knn.topk(candidates, query, N, query_filter=query_filter, item_filter=item_filter)
         if scalar:
@@ -77,6 +67,22 @@ class MatrixFactorizationBase(RecommenderBase):
         if items is not None:
             ids = items[ids]
         return ids, scores
+
+    # the two steps recommend() shares with implicit_amd.evaluation, which keeps the ids on the device
+    def _user_query(self, userid):
+        """The query rows of `userid` (scalar or array) as a device Matrix."""
+        if not np.isscalar(userid) and len(userid) > 1 and isinstance(userid, np.ndarray) and userid.dtype.kind in "iu" and \
+                userid[0] >= 0 and userid[-1] - userid[0] == len(userid) - 1 and (np.diff(userid) == 1).all():
+            # a run of consecutive ids (what batched callers pass): a row-range VIEW of the factors, no gather
+            if userid[-1] >= self.user_factors.shape[0]:
+                raise IndexError("row id out of range for selecting items from matrix")
+            return self.user_factors[int(userid[0]):int(userid[-1]) + 1]
+        return self.user_factors[userid]
+
+    @staticmethod
+    def _liked_filter(liked):
+        """The already-liked filter of a top-k query: the (row, col) pattern of the CSR matrix `liked`, None when empty."""
+        return gpu.COOMatrix.from_csr_pattern(liked) if liked.nnz else None  # the filter reads (row, col) only
 
     # ---- cosine similarity -------------------------------------------------------------------------
     def _similar(self, factors, norms_dev, norms_host, queryid, N, subset, filter_ids, what, query_factors=None):

@@ -258,6 +258,36 @@ int imp_spmat_destroy(imp_spmat *m);
 int imp_sparse_topk_product(const imp_spmat *A, const imp_spmat *B, int k, int zero_own_columns, int32_t *ids,
                             double *scores, int32_t *counts);
 
+/* ---- NEW: ranking metrics of recommendation rows (reference: the host loop of implicit/evaluation.pyx:366-475) ---------- */
+typedef struct imp_eval imp_eval; /* held-out pattern on the device + six running sums */
+/* Both entry points below take the held-out (test) matrix as a HOST CSR pattern: rows + 1 offsets starting at 0, int32 or
+ * int64 (`indptr_is_64`), int32 `indices`, every row strictly increasing inside [0, cols) (sorted, no duplicates); k, the
+ * length of a recommendation row; and two tables of k doubles, cg[i] = 1 / log2(i + 2) and its running sum (the caller
+ * computes them, the library never evaluates a logarithm).  IMP_INVALID_ARGUMENT: a row not strictly increasing, an index
+ * outside [0, cols), k < 1, a negative dimension, offsets that decrease or do not start at 0.
+ * The six sums, in this order: relevant (hits), pr_div (sum of min(k, likes)), sum_ap, sum_ndcg, sum_auc, total (rows
+ * counted); precision = relevant / pr_div, map / ndcg / auc = sum / total (evaluation.pyx:470-475).  Per row
+ * (csrc/eval_metrics.h): an id that is negative or >= cols is a miss; a row whose user has nothing held out adds nothing
+ * and is not counted. */
+/* Copies the pattern (64-bit offsets) and the tables to the device; the sums start at zero. */
+int imp_eval_create(int32_t rows, int32_t cols, const void *indptr, int indptr_is_64, const int32_t *indices, int k,
+                    const double *cg, const double *cg_sum, imp_eval **out);
+/* ids: n x k matrix of itemsize 4 holding int32 bit patterns (what imp_knn_topk writes into a device buffer); userids: the
+ * n rows of the pattern they were recommended for, any order, repeats allowed.  A user id outside [0, rows) is skipped
+ * like a user with nothing held out (never indexed with).  Queues two kernels on the library stream and returns without a
+ * host wait, unless per_row is given: a HOST array of n * 4 doubles that receives every row's hits and its ap, ndcg and
+ * auc terms (zeros for a skipped row).  No floating-point atomics: the same calls on the same data give the same bits. */
+int imp_eval_add(imp_eval *e, const imp_matrix *ids, const imp_intvector *userids, double *per_row);
+/* Waits for the library stream and reads the six sums. */
+int imp_eval_result(imp_eval *e, double *out);
+int imp_eval_reset(imp_eval *e);
+int imp_eval_destroy(imp_eval *e);
+/* Host code, no device involved: the same sums (written to sums[6], added up in row order) and per-row output for n rows
+ * of HOST ids (n x k int32) through the same per-row function.  IMP_OUT_OF_RANGE: a user id outside [0, rows). */
+int imp_host_ranking_metrics(int32_t rows, int32_t cols, const void *indptr, int indptr_is_64, const int32_t *indices, int k,
+                             const double *cg, const double *cg_sum, const int32_t *ids, const int32_t *userids, int64_t n,
+                             double *sums, double *per_row);
+
 /* ---- NEW: multi-GPU exchange over RCCL / xGMI (no reference counterpart) ------------------------ */
 /* One process per GPU.  Rank 0 calls imp_comm_unique_id, the host side broadcasts the 128 bytes by
  * any means (torch.distributed store, MPI, a file) and every rank calls imp_comm_init_rank. */
