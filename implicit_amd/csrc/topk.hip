@@ -1359,7 +1359,7 @@ extern "C" int imp_matrix_astype(const imp_matrix *src, size_t itemsize, imp_mat
 struct imp_knn {
   size_t max_temp_memory = 0;
   // screened emit path: multiplier (1, 2, 4) of the threshold pre-pass's subset stride, steered by the candidate counts of the
-  // previous batch of the same (catalogue size, k) -- see the feedback rule in imp_knn_topk
+  // previous batch of the same (catalogue size, k) -- see the feedback rule at emit_stride
   int stride_boost = 1;
   size_t boost_ni = 0;
   int boost_k = 0;
@@ -1369,7 +1369,7 @@ struct imp_knn {
   // persistent workspaces (grown on demand): no hipMalloc on the query path after the first call
   DeviceArray<float> scores, tile_max;
   DeviceArray<uint64_t> gcand;
-  DeviceArray<int32_t> dev_ids, counts, fallback;
+  DeviceArray<int32_t> dev_ids, fallback;
   DeviceArray<float> dev_dist;
   // emit path
   DeviceArray<float> sub_scores, fb_query, fb_dist;
@@ -1400,7 +1400,7 @@ struct imp_knn {
   DeviceArray<uint64_t> cand;
   DeviceArray<int32_t> fb_rows, fb_ids;
   // page-locked, device-addressable host memory of the emit path: fallback flags and (host outputs) ids / scores are written
-  // there by the kernels themselves (see imp_knn_topk)
+  // there by the kernels themselves (see OutputStage)
   struct Pinned {
     void *p = nullptr;
     size_t bytes = 0;
@@ -1422,6 +1422,485 @@ struct imp_knn {
     return a.data();
   }
 };
+
+// ---- host side of imp_knn_topk: checks -> operands -> outputs -> (emit | materialise) -> deliver ----------------------------
+// The A/B and parity switches of the top-k entry point, read from the environment once per process.  Every route they select
+// stays reachable: tests/test_gpu_topk_routes.py runs each of them.
+struct TopkSwitches {
+  bool fast;        // direct-operand MFMA GEMM (+ emit path, or tile maxima + single-pass pruned select); IMP_TOPK_NO_FAST set: general path
+  bool emit;        // emit path (no score matrix); IMP_TOPK_NO_EMIT set: its shapes materialise their scores
+  bool resident;    // fp16 two-term resident-query kernels; IMP_TOPK_RESIDENT=0: the six-product 128 x 128 kernel of rounds 3-4 (A/B, parity)
+  bool screen;      // screened emit pass; IMP_TOPK_SCREEN=0: three products
+  bool exact_mfma;  // IMP_TOPK_FP32_MFMA set: the exact-fp32 MFMA form (v_mfma_f32_32x32x2_f32) instead of the split-bf16 one (A/B, parity)
+  bool debug;       // IMP_TOPK_DEBUG set: the rows every batch hands to the exact path, on stderr
+};
+static const TopkSwitches &topk_switches() {
+  static const char *const resident = getenv("IMP_TOPK_RESIDENT"), *const screen = getenv("IMP_TOPK_SCREEN");
+  static const TopkSwitches s{getenv("IMP_TOPK_NO_FAST") == nullptr, getenv("IMP_TOPK_NO_EMIT") == nullptr, !(resident && atoi(resident) == 0),
+                              !(screen && atoi(screen) == 0), getenv("IMP_TOPK_FP32_MFMA") != nullptr, getenv("IMP_TOPK_DEBUG") != nullptr};
+  return s;
+}
+
+// grid of a 256-thread grid-stride kernel over n elements: at most per_cu workgroups per compute unit
+static int grid_1d(size_t n, int per_cu) { return (int)std::min<size_t>((n + 255) / 256, (size_t)ctx().num_cus * per_cu); }
+
+// Where the kernels write a call's ids and scores, and how they reach the caller.
+// Host outputs: the select kernels write ids and scores (and the emit path its fallback flags) STRAIGHT into page-locked
+// host memory the device can address -- [2048 flags][2048 counts][ids of the call][scores of the call] -- and after the host
+// wait they are simply there.  Any D2H copy instead costs more than the whole candidate sort: into pageable memory (the caller's
+// numpy arrays) the runtime stages it with a host wait of its own (three per emit call: ~0.1 of a 0.59 ms call), and an
+// ASYNCHRONOUS copy queued behind the kernels, page-locked or not, took ~0.4 ms to start on this stack (0.59 -> 1.0 ms
+// per call, gpurun_out/r4o, r4q).  Very large results (> 64 MB per array) keep the device buffers and the copies.
+constexpr size_t kFlagSlots = 2048;  // = query rows of an emit batch
+struct OutputStage {
+  int32_t *indices, *d_ids;  // the caller's array; what the kernels write: that array (device), its place in the page-locked stage or a device buffer
+  float *distances, *d_dist;
+  bool host_ids, host_dist, staged;
+  size_t out_words;
+  int *host_flags;   // emit path: one flag per row of the batch, read by the host after the batch's wait
+  int *host_counts;  // screened select: the length of every row's candidate list (feeds the stride rule)
+  void deliver() const {  // end of a call: wait, then hand the results over
+    if (staged) {
+      sync();
+      if (host_ids) std::copy(d_ids, d_ids + out_words, indices);
+      if (host_dist) std::copy(d_dist, d_dist + out_words, distances);
+    } else {
+      if (host_ids) IMP_CHECK_HIP(hipMemcpyAsync(indices, d_ids, out_words * 4, hipMemcpyDeviceToHost, stream()));
+      if (host_dist) IMP_CHECK_HIP(hipMemcpyAsync(distances, d_dist, out_words * 4, hipMemcpyDeviceToHost, stream()));
+      sync();
+    }
+  }
+};
+// a host output array's place in the stage, or a device buffer; `preset`: entries past k_eff keep the caller's initial values (topk.pyx:20-21)
+template <typename T> static T *place_output(const OutputStage &o, const T *caller, T *stage, DeviceArray<T> &dev, bool preset) {
+  if (o.staged) {
+    if (preset) std::copy(caller, caller + o.out_words, stage);
+    return stage;
+  }
+  T *d = imp_knn::ensure(dev, o.out_words);
+  if (preset) IMP_CHECK_HIP(hipMemcpyAsync(d, caller, o.out_words * 4, hipMemcpyHostToDevice, stream()));
+  return d;
+}
+static OutputStage stage_outputs(imp_knn *knn, size_t nq, int k, int k_eff, int32_t *indices, float *distances) {
+  OutputStage o{indices, indices, distances, distances, is_host_pointer(indices), is_host_pointer(distances), false, nq * (size_t)k, nullptr, nullptr};
+  o.staged = (o.host_ids || o.host_dist) && o.out_words <= ((size_t)16 << 20);
+  o.host_flags = static_cast<int *>(knn->host_stage.ensure((2 * kFlagSlots + (o.staged ? 2 * o.out_words : 0)) * 4));
+  o.host_counts = o.host_flags + kFlagSlots;
+  int *stage = o.host_flags + 2 * kFlagSlots;
+  if (o.host_ids) o.d_ids = place_output(o, indices, reinterpret_cast<int32_t *>(stage), knn->dev_ids, k_eff < k);
+  if (o.host_dist) o.d_dist = place_output(o, distances, reinterpret_cast<float *>(stage + o.out_words), knn->dev_dist, k_eff < k);
+  return o;
+}
+
+struct TopkCall {  // what a call computes once; every function below reads it
+  imp_knn *knn;
+  const imp_matrix *items_in;  // the item factors as the caller stored them (they name the cached item planes)
+  size_t nq, ni;
+  int f, k, k_eff, kpad;  // f: the factor count the kernels see (the caller's, or its zero-padded width on the 16-grid)
+  bool fast;              // direct-operand MFMA GEMM; false: the general path (any f, any k: LDS-staged GEMM + exact select)
+  bool use_lds;           // exact select: its kpad candidates fit in LDS
+  int stride, n_tiles;    // emit path: every stride-th 128-item block is scored by the threshold pre-pass; 64-item tiles of a score row
+  const float *norms;     // item norms (cosine scores) or null
+  const imp_coo *query_filter;       // null: none, or empty
+  const imp_intvector *item_filter;  // likewise
+  OutputStage out;
+};
+
+// The factors as the kernels read them: as stored (fp32, or fp16 on the direct-operand kernels, which convert in registers --
+// reference: SgemmEx on fp16 operands with fp32 accumulation, knn.cu:117-128), zero-padded fp32 copies in the handle's workspaces
+// (factor counts off the 16-grid ride the fast path on them: 272 K -> 1.1 M recs/s at f = 100, configs[2] items; the copies cost
+// ~0.1 ms per call at that size), or fp32 copies of fp16 factors (only the general path, any f, LDS-staged GEMM, scores those).
+struct TopkOperands {
+  const void *items, *query;
+  bool half;                                           // both are fp16 as stored
+  std::unique_ptr<imp_matrix> items_conv, query_conv;  // the converted copies live as long as the call
+};
+template <typename T> static void pad_factors(const imp_matrix *m, float *out, int f) {
+  pad_factor_rows_kernel<T><<<std::max(1, grid_1d(m->rows * (size_t)f, 16)), 256, 0, stream()>>>(static_cast<const T *>(m->data), out, m->rows, (int)m->cols, f);
+}
+static TopkOperands prepare_operands(imp_knn *knn, const imp_matrix *items_in, const imp_matrix *query_in, int f, bool fast) {
+  TopkOperands op{items_in->data, query_in->data, items_in->itemsize == 2, nullptr, nullptr};
+  if (f != (int)items_in->cols) {
+    float *pi = imp_knn::ensure(knn->pad_items, items_in->rows * (size_t)f), *pq = imp_knn::ensure(knn->pad_query, query_in->rows * (size_t)f);
+    IMP_PROF("pad_factors");
+    if (op.half) pad_factors<__half>(items_in, pi, f), pad_factors<__half>(query_in, pq, f);
+    else pad_factors<float>(items_in, pi, f), pad_factors<float>(query_in, pq, f);
+    IMP_CHECK_HIP(hipGetLastError());
+    op.items = pi, op.query = pq, op.half = false;
+  } else if (op.half && !fast) {
+    imp_matrix *t = nullptr;
+    if (imp_matrix_astype(items_in, 4, &t) != IMP_OK) throw std::runtime_error(imp_last_error());
+    op.items_conv.reset(t);
+    if (imp_matrix_astype(query_in, 4, &t) != IMP_OK) throw std::runtime_error(imp_last_error());
+    op.query_conv.reset(t);
+    op.items = op.items_conv->data, op.query = op.query_conv->data, op.half = false;
+  }
+  return op;
+}
+
+// fp16 two-term planes for the resident-query kernels (topk_resident.h): the item matrix once per catalogue version (cached in
+// the handle), the query rows of this call with one scale per row.  Returns the kernel arguments that name them, at query row 0
+template <typename TQ, typename TI> static ResidentArgs split_planes(const TopkCall &c, int KS, const TQ *Qb, const TI *Ib) {
+  IMP_PROF("split_query_rows");
+  const imp_matrix *items_in = c.items_in;
+  const size_t nq = c.nq, ni = c.ni, ni_pad = (ni + 127) / 128 * 128, F = (size_t)KS * 16;
+  const int f = c.f;
+  auto &ip = c.knn->item_planes;
+  const bool same = ip.key.src == items_in->data && ip.rows == ni && ip.cols == items_in->cols && ip.itemsize == items_in->itemsize && ip.KS == KS;
+  if (!same) {
+    ip.key.src = nullptr;
+    if (ip.planes.size < ni_pad * F * 2) ip.planes.alloc(ni_pad * F * 2);
+    if (ip.exp.size < 1) ip.exp.alloc(1), ip.maxbits.alloc(1), ip.ne.alloc(4);
+    if (ip.tile_n.size < ni_pad / 32) ip.tile_n.alloc(ni_pad / 32);
+    IMP_CHECK_HIP(hipMemsetAsync(ip.maxbits.data(), 0, sizeof(unsigned), stream()));
+    IMP_CHECK_HIP(hipMemsetAsync(ip.ne.data(), 0, 4 * sizeof(unsigned), stream()));
+    IMP_CHECK_HIP(hipMemsetAsync(ip.tile_n.data(), 0, (ni_pad / 32) * sizeof(unsigned), stream()));
+    rq_absmax_kernel<TI><<<std::max(1, grid_1d(ni * (size_t)f, 8)), 256, 0, stream()>>>(Ib, ni * (size_t)f, ip.maxbits.data());
+    rq_item_exp_kernel<<<1, 1, 0, stream()>>>(ip.maxbits.data(), ip.exp.data());
+    rq_split_items_kernel<TI><<<std::max(1, grid_1d(ni_pad * (F / 8), 16)), 256, 0, stream()>>>(Ib, ip.planes.data(), ni, ni_pad, f, KS, ip.exp.data());
+    rq_item_err_kernel<TI><<<(int)std::min<size_t>((ni + 3) / 4, (size_t)ctx().num_cus * 16), 256, 0, stream()>>>(Ib, ni, f, ip.exp.data(),
+                                                                                                              ip.ne.data(), ip.tile_n.data());
+    ip.rows = ni, ip.cols = items_in->cols, ip.itemsize = items_in->itemsize, ip.KS = KS;
+    const bool trusted = items_in->storage && items_in->storage->owned && !items_in->storage->exposed;
+    if (trusted) ip.key.src = items_in->data, ip.key.bytes = items_in->bytes();
+  }
+  const size_t nq_pad = rq_query_pad(nq);
+  _Float16 *qp = imp_knn::ensure(c.knn->query_planes, nq_pad * F * 2);
+  int *qe = imp_knn::ensure(c.knn->query_exp, nq_pad);
+  float *qerr = imp_knn::ensure(c.knn->query_err, 2 * nq_pad);
+  rq_split_queries_kernel<TQ><<<(int)std::min<size_t>((nq_pad + 3) / 4, (size_t)ctx().num_cus * 8), 256, 0, stream()>>>(Qb, qp, qe, nq, nq_pad, f, KS,
+                                                                                                                       qerr, qerr + nq_pad);
+  IMP_CHECK_HIP(hipGetLastError());
+  ResidentArgs ra{};
+  ra.qsplit = qp, ra.isplit = ip.planes.data(), ra.qexp = qe, ra.iexp = ip.exp.data(), ra.ni = (int)ni, ra.norms = c.norms;
+  ra.qa = qerr, ra.qb = qerr + nq_pad, ra.ine = ip.ne.data(), ra.tile_n = reinterpret_cast<const float *>(ip.tile_n.data());
+  return ra;
+}
+
+// a launch over `rows` query rows from `start`; the caller adds what its MODE writes (tile maxima or lists).  MODE 0 reads no qa .. tile_n / sub_cols
+static ResidentArgs resident_args(ResidentArgs ra, int KS, size_t start, int rows, int n_blocks, int block_stride, float *S) {
+  ra.qsplit += (start / 32) * (size_t)KS * 2 * 512, ra.qexp += start, ra.qa += start, ra.qb += start;
+  ra.nq = rows, ra.n_blocks = n_blocks, ra.block_stride = block_stride, ra.S = S, ra.sub_cols = n_blocks * 128;
+  return ra;
+}
+
+// the exact select of `rows` score rows (those flagged, or all); set_lds: the first launch of a loop sizes the kernel's LDS
+static void launch_select_exact(const TopkCall &c, bool set_lds, const float *scores, int rows, int32_t *ids, float *dist, uint64_t *gcand, const int *flagged) {
+  const size_t lds = c.use_lds ? (size_t)c.kpad * 8 : 0;
+  auto kern = select_kernel<512>;
+  if (set_lds)
+    IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(lds, 1)));
+  kern<<<(unsigned)rows, 512, lds, stream()>>>(scores, (int)c.ni, c.k_eff, c.kpad, ids, dist, c.k, gcand, c.use_lds ? 1 : 0, flagged);
+  IMP_CHECK_HIP(hipGetLastError());
+}
+
+// ---- emit path (no score matrix): large item sets, k small against the candidate lists ---------------------------------------
+// one GEMM launch of a batch (MODE 1: subset scores, 2: three-product emit pass, 3: screened emit pass): on the resident planes
+// (`planes`, else null), on query rows pre-split for the six-product kernel (`qs`, else null) or on the rows in their storage type
+template <int M, typename TQ, typename TI, bool BF3>
+static void emit_gemm(const TopkCall &c, const ResidentArgs *planes, int KS, const split_bf16 *qs, const TQ *Qb, const TI *Ib, size_t start, dim3 grid,
+                      int rows, float *S_out, int bstride, const EmitArgs &ea) {
+  if (planes) {
+    ResidentArgs ra = resident_args(*planes, KS, start, rows, (int)grid.x, bstride, S_out);
+    ra.emit = ea;
+    launch_score_resident<M>(KS, ra, rows);
+  } else if constexpr (M == 3) {
+    throw std::logic_error("the screened emit pass exists in the resident form only");
+  } else if (qs) {
+    score_gemm_direct_kernel<M, split_bf16, TI, true><<<grid, 256, 0, stream()>>>(qs + start * 3 * (size_t)c.f, rows, Ib, (int)c.ni, c.f, c.norms, S_out,
+                                                                            nullptr, 0, bstride, ea);
+  } else {
+    score_gemm_direct_kernel<M, TQ, TI, BF3><<<grid, 256, 0, stream()>>>(Qb + start * c.f, rows, Ib, (int)c.ni, c.f, c.norms, S_out, nullptr, 0, bstride, ea);
+  }
+}
+
+static void clear_row_bits(const TopkCall &c, uint32_t *row_bits, size_t start, size_t end) {  // behind a batch: the words it set, back to zero
+  const imp_coo *qf = c.query_filter;
+  coo_bitmap_clear_kernel<<<grid_1d((size_t)qf->nnz, 8), 256, 0, stream()>>>(row_bits, (int)((c.ni + 31) / 32), (int)start, (int)end, (int)c.ni,
+                                                                            qf->row.data(), qf->col.data(), (size_t)qf->nnz);
+  IMP_CHECK_HIP(hipGetLastError());
+  c.knn->row_bits_dirty = false;
+}
+
+static void scan_flags(const int *flags, size_t rows, std::vector<int32_t> &fb_list) {  // the rows a batch's select flagged for the exact path
+  fb_list.clear();
+  for (size_t i = 0; i < rows; ++i)
+    if (flags[i]) fb_list.push_back((int32_t)i);
+}
+
+// the rows of the batch at `start` whose list overflowed, came up short or tied exactly at the k-th score: materialised FB rows at a time
+template <typename TQ, typename TI, bool BF3>
+static void emit_fallback_rows(const TopkCall &c, const TQ *qptr, const TI *Ib, size_t start, const std::vector<int32_t> &fb_list,
+                               const uint32_t *row_bits, const uint32_t *item_bits) {
+  IMP_PROF("topk_fallback");
+  constexpr int FB = 64;  // fallback rows per materialised group
+  imp_knn *knn = c.knn;
+  const int ni = (int)c.ni, f = c.f, k = c.k, n_tiles = c.n_tiles;
+  int32_t *d_rows = imp_knn::ensure(knn->fb_rows, fb_list.size());
+  IMP_CHECK_HIP(hipMemcpyAsync(d_rows, fb_list.data(), fb_list.size() * 4, hipMemcpyHostToDevice, stream()));
+  float *fbq = imp_knn::ensure(knn->fb_query, (size_t)FB * f);
+  float *fscores = imp_knn::ensure(knn->scores, (size_t)FB * c.ni);
+  float *ftile = imp_knn::ensure(knn->tile_max, (size_t)FB * n_tiles);
+  int32_t *fids = imp_knn::ensure(knn->fb_ids, (size_t)FB * k);
+  float *fdist = imp_knn::ensure(knn->fb_dist, (size_t)FB * k);
+  uint64_t *fg = c.use_lds ? nullptr : imp_knn::ensure(knn->gcand, (size_t)FB * c.kpad);
+  for (size_t g0 = 0; g0 < fb_list.size(); g0 += FB) {
+    const int n = (int)std::min<size_t>(FB, fb_list.size() - g0);
+    gather_query_rows_kernel<TQ><<<std::max(1, (n * f + 255) / 256), 256, 0, stream()>>>(qptr, d_rows + g0, n, f, fbq);
+    score_gemm_direct_kernel<0, float, TI, BF3><<<dim3((unsigned)((c.ni + 127) / 128), 1), 256, 0, stream()>>>(fbq, n, Ib, ni, f, c.norms, fscores, ftile,
+                                                                                                           n_tiles, 1, EmitArgs{});
+    if (row_bits || item_bits)
+      bitmap_filter_kernel<<<grid_1d((size_t)n * n_tiles, 8), 256, 0, stream()>>>(fscores, ftile, ni, n_tiles, d_rows + g0, n, row_bits, item_bits,
+                                                                                 (int)((c.ni + 31) / 32));
+    launch_select_exact(c, g0 == 0, fscores, n, fids, fdist, fg, nullptr);
+    scatter_topk_rows_kernel<<<std::max(1, (n * k + 255) / 256), 256, 0, stream()>>>(fids, fdist, d_rows + g0, n, k, c.out.d_ids + start * k,
+                                                                                 c.out.d_dist + start * k);
+    IMP_CHECK_HIP(hipGetLastError());
+  }
+}
+
+template <typename TQ, typename TI, bool BF3> static void emit_route(const TopkCall &c, const TQ *Qb, const TI *Ib) {
+  imp_knn *knn = c.knn;
+  const TopkSwitches &sw = topk_switches();
+  const size_t nq = c.nq, ebatch = std::min<size_t>(nq, kFlagSlots);  // (one flag per row of a batch)
+  const int ni = (int)c.ni, f = c.f, k = c.k, k_eff = c.k_eff, stride = c.stride;
+  const imp_coo *qf = c.query_filter;
+  const imp_intvector *itf = c.item_filter;
+  const int words = (int)((c.ni + 31) / 32), n_blocks = (int)((c.ni + 127) / 128), n_sub = (n_blocks + stride - 1) / stride, sub_cols = n_sub * 128;
+  float *sub = imp_knn::ensure(knn->sub_scores, ebatch * (size_t)sub_cols);
+  uint32_t *tau = imp_knn::ensure(knn->tau, (ebatch + 127) / 128 * 128);  // the emit epilogue loads thresholds four rows at a time
+  unsigned int *cnt = imp_knn::ensure(knn->cand_count, ebatch);
+  uint64_t *cand = imp_knn::ensure(knn->cand, ebatch * (size_t)kEmitCap);
+  float *row_unscale = imp_knn::ensure(knn->row_unscale, rq_query_pad(ebatch));
+  int *flags = c.out.host_flags, *list_len = c.out.host_counts;
+  if (qf && knn->row_bits.size < ebatch * (size_t)words) knn->row_bits_dirty = true;  // (regrown: fresh memory)
+  uint32_t *row_bits = qf ? imp_knn::ensure(knn->row_bits, ebatch * (size_t)words) : nullptr;
+  uint32_t *item_bits = itf ? imp_knn::ensure(knn->item_bits, (size_t)words) : nullptr;
+  if (itf) IMP_CHECK_HIP(hipMemsetAsync(item_bits, 0, (size_t)words * 4, stream()));
+  // fp16 two-term form with the queries resident in registers and the item planes cached (topk_resident.h): every factor count
+  // that pads to 32 / 64 / 128 / 256; fp16-stored factors too (their values are their own high halves: scores stay bit-identical
+  // to scoring fp32 copies of them).  IMP_TOPK_RESIDENT=0: the six-product 128 x 128 kernel of rounds 3-4 (A/B, parity)
+  const int KS = rq_ks_for(f);
+  const bool resident = BF3 && sw.resident && KS > 0;
+  ResidentArgs plane_args{};
+  split_bf16 *qs = nullptr;
+  if (resident) {
+    plane_args = split_planes(c, KS, Qb, Ib);
+  } else if (BF3) {
+    IMP_PROF("split_query_rows");
+    const size_t nq_pad = (nq + 127) / 128 * 128;  // whole 128-row query blocks: a workgroup reads all four tiles of its block
+    qs = imp_knn::ensure(knn->query_split, nq_pad * 3 * (size_t)f);
+    split_query_rows_kernel<TQ><<<std::max(1, grid_1d(nq_pad * (size_t)f, 16)), 256, 0, stream()>>>(Qb, reinterpret_cast<__bf16 *>(qs), nq, nq_pad, f);
+    IMP_CHECK_HIP(hipGetLastError());
+  }
+  const ResidentArgs *planes = resident ? &plane_args : nullptr;
+  float *unscale = resident ? row_unscale : nullptr;
+  // screened emit pass (topk_resident.h MODE 3): one-product scores against tau - eps, the few candidates that can still be among
+  // the best k re-scored in fp32 by the select kernel.  Dot-product scores only (no item norms); IMP_TOPK_SCREEN=0: three products
+  const bool screen = resident && sw.screen && !c.norms;
+  float *row_eps = screen ? imp_knn::ensure(knn->row_eps, rq_query_pad(ebatch)) : nullptr;
+  std::vector<int32_t> fb_list;
+  for (size_t start = 0; start < nq; start += ebatch) {
+    const size_t end = std::min(nq, start + ebatch), rows = end - start;
+    const dim3 sub_grid((unsigned)n_sub, (unsigned)((rows + 127) / 128)), full_grid((unsigned)n_blocks, (unsigned)((rows + 127) / 128));
+    int32_t *ids = c.out.d_ids + start * k;
+    float *dist = c.out.d_dist + start * k;
+    if (qf) {
+      if (knn->row_bits_dirty) IMP_CHECK_HIP(hipMemsetAsync(row_bits, 0, knn->row_bits.size * sizeof(uint32_t), stream()));
+      knn->row_bits_dirty = true;  // (until this batch's clear is queued)
+    }
+    {
+      IMP_PROF("score_gemm_subset");
+      emit_gemm<1, TQ, TI, BF3>(c, planes, KS, qs, Qb, Ib, start, sub_grid, (int)rows, sub, stride, EmitArgs{});
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    if (itf) {
+      IMP_PROF("item_filter");
+      item_bitmap_kernel<<<grid_1d(itf->size, 8), 256, 0, stream()>>>(item_bits, ni, itf->v.data(), (int)itf->size, sub, (int)rows, sub_cols, stride);
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    if (qf) {
+      IMP_PROF("coo_filter");
+      coo_bitmap_kernel<<<grid_1d((size_t)qf->nnz, 8), 256, 0, stream()>>>(row_bits, words, (int)start, (int)end, ni, qf->row.data(), qf->col.data(),
+                                                                          (size_t)qf->nnz, sub, sub_cols, stride);
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    {
+      IMP_PROF("topk_threshold");
+      if (k_eff <= 32) subset_threshold_groupmax_kernel<256><<<(unsigned)rows, 256, 0, stream()>>>(sub, sub_cols, k_eff, tau, cnt);
+      else subset_threshold_kernel<512><<<(unsigned)rows, 512, 0, stream()>>>(sub, sub_cols, k_eff, tau, cnt);
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    {
+      IMP_PROF("score_gemm");
+      EmitArgs ea{tau, row_bits, item_bits, words, cand, cnt, kEmitCap, unscale, row_eps};
+      if (screen) emit_gemm<3, TQ, TI, BF3>(c, planes, KS, qs, Qb, Ib, start, full_grid, (int)rows, nullptr, 1, ea);
+      else emit_gemm<2, TQ, TI, BF3>(c, planes, KS, qs, Qb, Ib, start, full_grid, (int)rows, nullptr, 1, ea);
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    {
+      IMP_PROF("topk_select_candidates");
+      if (screen)
+        select_screened_kernel<512, TQ, TI><<<(unsigned)rows, 512, 0, stream()>>>(cand, cnt, kEmitCap, k_eff, ids, dist, k, flags, row_eps, Qb + start * f,
+                                                                                 Ib, f, list_len);
+      else
+        select_candidates_kernel<512><<<(unsigned)rows, 512, 0, stream()>>>(cand, cnt, kEmitCap, k_eff, ids, dist, k, flags, unscale);
+      IMP_CHECK_HIP(hipGetLastError());
+#ifdef RQ_SCREEN_STATS
+      if (screen) {
+        unsigned long long h[4];
+        IMP_CHECK_HIP(hipStreamSynchronize(stream()));
+        IMP_CHECK_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(rq_screen_stats), sizeof(h)));
+        fprintf(stderr, "[screen-stats] rows %llu, candidates per row %.1f, re-scored per row %.1f (largest so far: %llu)\n", h[0],
+                (double)h[1] / std::max(1ull, h[0]), (double)h[2] / std::max(1ull, h[0]), h[3]);
+      }
+#endif
+    }
+    sync();
+    scan_flags(flags, rows, fb_list);
+    if (screen && fb_list.size() * 8 > rows) {
+      // The screen separated nothing for much of this batch: scores so concentrated that an 11-bit product cannot tell the
+      // best k from the bulk (factors a sweep or two from an all-positive start: every score within 1e-3 of the next) -- the
+      // lists overflowed.  The WHOLE batch is redone by the three-product emit pass with its exact threshold test (same
+      // thresholds, lists reset) before anything goes to the row-by-row exact path: 0.25 ms per 1000 rows instead of 1.3.
+      // Decided by this batch's own outcome, not by the handle's history: the same call gives the same bits every time.
+      IMP_PROF("topk_exact_emit_retry");
+      IMP_CHECK_HIP(hipMemsetAsync(cnt, 0, rows * sizeof(unsigned int), stream()));
+      EmitArgs ea{tau, row_bits, item_bits, words, cand, cnt, kEmitCap, row_unscale, nullptr};
+      emit_gemm<2, TQ, TI, BF3>(c, planes, KS, qs, Qb, Ib, start, full_grid, (int)rows, nullptr, 1, ea);
+      select_candidates_kernel<512><<<(unsigned)rows, 512, 0, stream()>>>(cand, cnt, kEmitCap, k_eff, ids, dist, k, flags, row_unscale);
+      IMP_CHECK_HIP(hipGetLastError());
+      sync();
+      scan_flags(flags, rows, fb_list);
+    }
+    if (screen && rows >= 64) {  // the stride rule (emit_stride): mean list length and exact-path rows of this batch
+      size_t total = 0;
+      for (size_t i = 0; i < rows; ++i) total += (size_t)list_len[i];
+      const size_t mean = total / rows;
+      if (fb_list.size() * 100 > rows || mean > 400) knn->stride_boost = std::max(1, knn->stride_boost / 2);
+      else if (mean < 48 && knn->stride_boost < 4) knn->stride_boost *= 2;
+    }
+    if (sw.debug && !fb_list.empty()) {
+      std::vector<uint32_t> hc(rows), ht(rows);
+      IMP_CHECK_HIP(hipMemcpy(hc.data(), cnt, rows * 4, hipMemcpyDeviceToHost));
+      IMP_CHECK_HIP(hipMemcpy(ht.data(), tau, rows * 4, hipMemcpyDeviceToHost));
+      fprintf(stderr, "[topk-debug] batch at %zu: %zu fallback rows:", start, fb_list.size());
+      for (size_t i = 0; i < std::min<size_t>(fb_list.size(), 8); ++i)
+        fprintf(stderr, " (row %d count %u tau-key %08x)", fb_list[i], hc[fb_list[i]], ht[fb_list[i]]);
+      fprintf(stderr, "\n");
+    }
+    if (!fb_list.empty()) emit_fallback_rows<TQ, TI, BF3>(c, Qb + start * f, Ib, start, fb_list, row_bits, item_bits);
+    if (qf && end < nq) clear_row_bits(c, row_bits, start, end);  // (the last batch's: behind the call's wait, below)
+  }
+  c.out.deliver();
+  if (qf) clear_row_bits(c, row_bits, (nq - 1) / ebatch * ebatch, nq);
+}
+
+// ---- materialising path: a batch of score rows, the filters on them, pruned select, exact select of the rows it flagged --------
+template <typename TQ, typename TI, bool BF3> static void materialise_route(const TopkCall &c, const TQ *Qb, const TI *Ib) {
+  imp_knn *knn = c.knn;
+  const int ni = (int)c.ni, f = c.f, k = c.k, n_tiles = c.n_tiles;
+  const bool fast = c.fast;
+  const imp_coo *qf = c.query_filter;
+  const imp_intvector *itf = c.item_filter;
+  const size_t nq = c.nq, temp = std::min<size_t>(knn->max_temp_memory, (size_t)4 << 30);
+  size_t batch = std::max<size_t>(1, std::min<size_t>(nq, temp / (sizeof(float) * c.ni)));
+  // a resident launch reads whole 128-row blocks of query planes from its first row on: batches start on that grid, or use the direct kernel
+  const int KS = rq_ks_for(f);
+  const bool resident = BF3 && fast && topk_switches().resident && KS > 0 && (batch == nq || batch >= 128);
+  if (resident && batch < nq) batch = batch / 128 * 128;
+  float *scores = imp_knn::ensure(knn->scores, batch * c.ni);
+  uint64_t *gcand = c.use_lds ? nullptr : imp_knn::ensure(knn->gcand, batch * (size_t)c.kpad);
+  float *tile_max = fast ? imp_knn::ensure(knn->tile_max, batch * (size_t)n_tiles) : nullptr;
+  int *fallback = fast ? imp_knn::ensure(knn->fallback, batch) : nullptr;
+  const ResidentArgs planes = resident ? split_planes(c, KS, Qb, Ib) : ResidentArgs{};
+  for (size_t start = 0; start < nq; start += batch) {
+    const size_t end = std::min(nq, start + batch), rows = end - start;
+    int32_t *ids = c.out.d_ids + start * k;
+    float *dist = c.out.d_dist + start * k;
+    if (resident) {
+      IMP_PROF("score_gemm");
+      ResidentArgs ra = resident_args(planes, KS, start, (int)rows, (int)((c.ni + 127) / 128), 1, scores);
+      ra.tile_max = tile_max, ra.n_tiles64 = n_tiles;
+      launch_score_resident<0>(KS, ra, (int)rows);
+    } else if (fast) {
+      IMP_PROF("score_gemm");
+      dim3 grid((unsigned)((c.ni + 127) / 128), (unsigned)((rows + 127) / 128));
+      score_gemm_direct_kernel<0, TQ, TI, BF3><<<grid, 256, 0, stream()>>>(Qb + start * f, (int)rows, Ib, ni, f, c.norms, scores, tile_max, n_tiles, 1,
+                                                                          EmitArgs{});
+      IMP_CHECK_HIP(hipGetLastError());
+    } else {
+      IMP_PROF("score_gemm_lds");
+      dim3 grid((unsigned)((c.ni + kBN - 1) / kBN), (unsigned)((rows + kBM - 1) / kBM));
+      if constexpr (std::is_same<TQ, float>::value) {  // the general path always runs on fp32 (copies of fp16 factors)
+        score_gemm_kernel<<<grid, 256, 0, stream()>>>(Qb + start * f, (int)rows, Ib, ni, f, c.norms, scores);
+        IMP_CHECK_HIP(hipGetLastError());
+      }
+    }
+    if (itf) {
+      IMP_PROF("item_filter");
+      item_filter_kernel<<<grid_1d(rows * itf->size, 8), 256, 0, stream()>>>(scores, (int)rows, ni, itf->v.data(), (int)itf->size);
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    if (qf) {
+      IMP_PROF("coo_filter");
+      coo_filter_kernel<<<grid_1d((size_t)qf->nnz, 8), 256, 0, stream()>>>(scores, (int)start, (int)end, ni, qf->row.data(), qf->col.data(), (size_t)qf->nnz);
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    if (fast && (itf || qf)) {
+      // second phase (all filter writes are done): refresh the maxima of the touched tiles
+      IMP_PROF("filter_tile_refresh");
+      if (itf)
+        item_filter_refresh_kernel<<<grid_1d(rows * itf->size, 8), 256, 0, stream()>>>(scores, tile_max, (int)rows, ni, n_tiles, itf->v.data(), (int)itf->size);
+      if (qf)
+        coo_filter_refresh_kernel<<<grid_1d((size_t)qf->nnz, 8), 256, 0, stream()>>>(scores, tile_max, (int)start, (int)end, ni, n_tiles, qf->row.data(),
+                                                                                    qf->col.data(), (size_t)qf->nnz);
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    if (fast) {
+      IMP_PROF("topk_select_pruned");
+      // (extra = 0, filter_counts = null: the tile maxima are refreshed after the filters, so no slack for filtered entries is needed)
+      select_pruned_kernel<512><<<(unsigned)rows, 512, 0, stream()>>>(scores, tile_max, ni, n_tiles, c.k_eff, 0, nullptr, ids, dist, k, fallback);
+      IMP_CHECK_HIP(hipGetLastError());
+    }
+    {
+      IMP_PROF("topk_select");
+      launch_select_exact(c, true, scores, (int)rows, ids, dist, gcand, fallback);
+    }
+    if (topk_switches().debug && fast) {  // how many rows the pruned select handed to the exact select
+      std::vector<int> hf(rows);
+      IMP_CHECK_HIP(hipMemcpy(hf.data(), fallback, rows * sizeof(int), hipMemcpyDeviceToHost));
+      size_t nfb = 0, first_fb = 0;
+      for (size_t i = rows; i-- > 0;)
+        if (hf[i]) first_fb = i, ++nfb;
+      fprintf(stderr, "[topk-debug] materialising batch at %zu: %zu of %zu rows re-done by the exact select (first: row %zu)\n", start, nfb, rows, first_fb);
+    }
+  }
+  c.out.deliver();
+}
+
+// The stride of the emit path's threshold pre-pass.  The emit path pays when the candidate lists stay SPARSE: every `stride`-th 128-item block is scored first and
+// about stride x k entries per query survive its threshold.  The stride is chosen so that they fill at most half of a
+// query's kEmitCap slots AND are at most one in 64 of the items -- every 64-item tile with a survivor costs an atomic on
+// the query's counter and a scattered store (measured at configs[4]'s similar_items shape, 26 744 items, k = 100,
+// stride 20: 7.5 % of all scores survive and the emit GEMM runs at 10 TFLOP/s against 33 for the materialising path) --
+// and a stride below 8 (a pre-pass of more than an eighth of the GEMM) is not worth it either.
+// The stride is a trade between the pre-pass (scores of 1 / stride of the items materialised, filtered, selected from) and the
+// candidate lists (about stride x k entries on unstructured data).  On TRAINED factors a row's best scores stand far above the
+// bulk and the lists stay short (22 entries at stride 32 on the bench's factors), so the screened path lets the stride grow:
+// after every batch the mean list length decides -- under 48: twice the stride next time (up to 4 x 32), over 400 or more than
+// one row in a hundred sent to the exact path: half.  Results do not depend on the stride; random factors stay at 32
+// (stride 128 there: 1280-entry lists and every row's staging overflowing -- measured, profiles/r06_topk_resident_knockouts.txt).
+static int emit_stride(imp_knn *knn, size_t ni, int k_eff, bool cosine) {
+  if (knn->boost_ni != ni || knn->boost_k != k_eff) knn->stride_boost = 1, knn->boost_ni = ni, knn->boost_k = k_eff;
+  const int stride_cap = cosine ? kSubStride : kSubStride * knn->stride_boost;
+  return (int)std::min<size_t>(std::min(stride_cap, kEmitCap / (2 * std::max(1, k_eff))), ni / ((size_t)64 * std::max(1, k_eff)));
+}
+
+template <typename T, bool BF3> static void topk_route(const TopkCall &c, bool emit, const TopkOperands &op) {
+  const T *Qb = static_cast<const T *>(op.query), *Ib = static_cast<const T *>(op.items);
+  emit ? emit_route<T, T, BF3>(c, Qb, Ib) : materialise_route<T, T, BF3>(c, Qb, Ib);
+}
 
 extern "C" {
 
@@ -1455,506 +1934,26 @@ int imp_knn_topk(imp_knn *knn, const imp_matrix *items_in, const imp_matrix *que
     const int f_in = (int)items_in->cols;
     if (nq == 0 || k == 0) return;
     if (ni > (size_t)INT32_MAX) throw std::invalid_argument("too many items for topk");
-
+    const TopkSwitches &sw = topk_switches();
     const int k_eff = (int)std::min<size_t>((size_t)k, ni);
-    // fast path: direct-operand MFMA GEMM (+ emit path, or tile maxima + single-pass pruned select)
-    static const bool no_fast = getenv("IMP_TOPK_NO_FAST") != nullptr;
-    // factor counts off the 16-grid ride the fast path on zero-padded fp32 copies (272 K -> 1.1 M recs/s at f = 100, configs[2]
-    // items; the copies cost ~0.1 ms per call at that size)
-    const bool padded = !no_fast && f_in % 16 != 0 && f_in >= 1 && k_eff <= kCandCap;
+    const bool padded = sw.fast && f_in % 16 != 0 && f_in >= 1 && k_eff <= kCandCap;  // (see TopkOperands)
     const int f = padded ? (f_in + 15) / 16 * 16 : f_in;
-    const bool fast = !no_fast && (f % 8 == 0) && k_eff <= kCandCap;
-    // fp16 factors (reference: SgemmEx on fp16 operands with fp32 accumulation, knn.cu:117-128): the direct-operand kernels
-    // read them as stored and convert in registers; only the general path (any f, LDS-staged GEMM) scores an fp32 copy
-    const bool half_direct = items_in->itemsize == 2 && fast && !padded;
-    std::unique_ptr<imp_matrix> items_conv, query_conv;
-    const imp_matrix *items = items_in, *query = query_in;
-    imp_matrix items_pad, query_pad;  // views of the padded workspaces (no ownership)
-    if (padded) {
-      float *pi = imp_knn::ensure(knn->pad_items, ni * (size_t)f), *pq = imp_knn::ensure(knn->pad_query, nq * (size_t)f);
-      IMP_PROF("pad_factors");
-      auto grid = [&](size_t n) { return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)ctx().num_cus * 16)); };
-      if (items_in->itemsize == 4) {
-        pad_factor_rows_kernel<float><<<grid(ni * f), 256, 0, stream()>>>(items_in->f32(), pi, ni, f_in, f);
-        pad_factor_rows_kernel<float><<<grid(nq * f), 256, 0, stream()>>>(query_in->f32(), pq, nq, f_in, f);
-      } else {
-        pad_factor_rows_kernel<__half><<<grid(ni * f), 256, 0, stream()>>>(reinterpret_cast<const __half *>(items_in->data), pi, ni, f_in, f);
-        pad_factor_rows_kernel<__half><<<grid(nq * f), 256, 0, stream()>>>(reinterpret_cast<const __half *>(query_in->data), pq, nq, f_in, f);
-      }
-      IMP_CHECK_HIP(hipGetLastError());
-      items_pad.rows = ni, items_pad.cols = (size_t)f, items_pad.itemsize = 4, items_pad.data = pi;
-      query_pad.rows = nq, query_pad.cols = (size_t)f, query_pad.itemsize = 4, query_pad.data = pq;
-      items = &items_pad;
-      query = &query_pad;
-    } else if (items_in->itemsize == 2 && !half_direct) {
-      imp_matrix *t = nullptr;
-      if (imp_matrix_astype(items_in, 4, &t) != IMP_OK) throw std::runtime_error(imp_last_error());
-      items_conv.reset(t);
-      if (imp_matrix_astype(query_in, 4, &t) != IMP_OK) throw std::runtime_error(imp_last_error());
-      query_conv.reset(t);
-      items = items_conv.get();
-      query = query_conv.get();
-    }
+    const bool fast = sw.fast && (f % 8 == 0) && k_eff <= kCandCap;
+    const TopkOperands op = prepare_operands(knn, items_in, query_in, f, fast);
     int kpad = 1;
     while (kpad < k_eff) kpad <<= 1;
     if (kpad < 2) kpad = 2;
-
-    const bool host_ids = is_host_pointer(indices), host_dist = is_host_pointer(distances);
-    int32_t *d_ids = indices;
-    float *d_dist = distances;
-    // Host outputs: the select kernels write ids and scores (and the emit path its fallback flags) STRAIGHT into page-locked
-    // host memory the device can address -- [2048 flags][ids of the call][scores of the call] -- and after the host wait they
-    // are simply there.  Any D2H copy instead costs more than the whole candidate sort: into pageable memory (the caller's
-    // numpy arrays) the runtime stages it with a host wait of its own (three per emit call: ~0.1 of a 0.59 ms call), and an
-    // ASYNCHRONOUS copy queued behind the kernels, page-locked or not, took ~0.4 ms to start on this stack (0.59 -> 1.0 ms
-    // per call, gpurun_out/r4o, r4q).  Very large results (> 64 MB per array) keep the device buffers and the copies.
-    constexpr size_t kFlagSlots = 2048;  // = the emit path's batch
-    const size_t out_words = nq * (size_t)k;
-    const bool stage_results = (host_ids || host_dist) && out_words <= ((size_t)16 << 20);
-    int *host_flags = static_cast<int *>(knn->host_stage.ensure((2 * kFlagSlots + (stage_results ? 2 * out_words : 0)) * 4));
-    int *host_counts = host_flags + kFlagSlots;  // screened select: the length of every row's candidate list (feeds the stride rule)
-    int32_t *stage_ids = reinterpret_cast<int32_t *>(host_flags + 2 * kFlagSlots);
-    float *stage_dist = reinterpret_cast<float *>(host_flags + 2 * kFlagSlots + out_words);
-    if (host_ids) {
-      if (stage_results) {
-        d_ids = stage_ids;
-        if (k_eff < k) std::copy(indices, indices + out_words, stage_ids);  // entries past k_eff keep the caller's initial values (topk.pyx:20-21 zero-fills them)
-      } else {
-        d_ids = imp_knn::ensure(knn->dev_ids, out_words);
-        if (k_eff < k) IMP_CHECK_HIP(hipMemcpyAsync(d_ids, indices, out_words * 4, hipMemcpyHostToDevice, stream()));
-      }
-    }
-    if (host_dist) {
-      if (stage_results) {
-        d_dist = stage_dist;
-        if (k_eff < k) std::copy(distances, distances + out_words, stage_dist);
-      } else {
-        d_dist = imp_knn::ensure(knn->dev_dist, out_words);
-        if (k_eff < k) IMP_CHECK_HIP(hipMemcpyAsync(d_dist, distances, out_words * 4, hipMemcpyHostToDevice, stream()));
-      }
-    }
-    auto deliver = [&] {  // end of a call: wait, then hand the results over
-      if (stage_results) {
-        sync();
-        if (host_ids) std::copy(stage_ids, stage_ids + out_words, indices);
-        if (host_dist) std::copy(stage_dist, stage_dist + out_words, distances);
-      } else {
-        if (host_ids) IMP_CHECK_HIP(hipMemcpyAsync(indices, d_ids, out_words * 4, hipMemcpyDeviceToHost, stream()));
-        if (host_dist) IMP_CHECK_HIP(hipMemcpyAsync(distances, d_dist, out_words * 4, hipMemcpyDeviceToHost, stream()));
-        sync();
-      }
-    };
-
-    size_t temp = std::min<size_t>(knn->max_temp_memory, (size_t)4 << 30);
-    size_t batch = std::max<size_t>(1, std::min<size_t>(nq, temp / (sizeof(float) * ni)));
-    static const bool no_emit_alloc = getenv("IMP_TOPK_NO_EMIT") != nullptr;
-    // emit path (no score matrix) when the candidate lists stay SPARSE: every `stride`-th 128-item block is scored first and
-    // about stride x k entries per query survive its threshold.  The stride is chosen so that they fill at most half of a
-    // query's kEmitCap slots AND are at most one in 64 of the items -- every 64-item tile with a survivor costs an atomic on
-    // the query's counter and a scattered store (measured at configs[4]'s similar_items shape, 26 744 items, k = 100,
-    // stride 20: 7.5 % of all scores survive and the emit GEMM runs at 10 TFLOP/s against 33 for the materialising path) --
-    // and a stride below 8 (a pre-pass of more than an eighth of the GEMM) is not worth it either.
-    // The stride is a trade between the pre-pass (scores of 1 / stride of the items materialised, filtered, selected from) and the
-    // candidate lists (about stride x k entries on unstructured data).  On TRAINED factors a row's best scores stand far above the
-    // bulk and the lists stay short (22 entries at stride 32 on the bench's factors), so the screened path lets the stride grow:
-    // after every batch the mean list length decides -- under 48: twice the stride next time (up to 4 x 32), over 400 or more than
-    // one row in a hundred sent to the exact path: half.  Results do not depend on the stride; random factors stay at 32
-    // (stride 128 there: 1280-entry lists and every row's staging overflowing -- measured, profiles/r06_topk_resident_knockouts.txt).
-    if (knn->boost_ni != ni || knn->boost_k != k_eff) knn->stride_boost = 1, knn->boost_ni = ni, knn->boost_k = k_eff;
-    const int stride_cap = item_norms ? kSubStride : kSubStride * knn->stride_boost;
-    const int stride = (int)std::min<size_t>(std::min(stride_cap, kEmitCap / (2 * std::max(1, k_eff))), ni / ((size_t)64 * std::max(1, k_eff)));
-    const bool emit_shape = (f % 8 == 0) && k_eff == k && k_eff <= 256 && stride >= 8;
-    const bool will_emit = !no_emit_alloc && getenv("IMP_TOPK_NO_FAST") == nullptr && emit_shape;
-    float *scores = will_emit ? nullptr : imp_knn::ensure(knn->scores, batch * ni);  // the emit path materialises fallback rows only
-    const bool use_lds = (size_t)kpad * 8 <= 96 * 1024;
-    uint64_t *gcand = use_lds ? nullptr : imp_knn::ensure(knn->gcand, batch * (size_t)kpad);
-
-    const int n_tiles = (int)((ni + kTileItems - 1) / kTileItems);
-    float *tile_max = (fast && !will_emit) ? imp_knn::ensure(knn->tile_max, batch * (size_t)n_tiles) : nullptr;
-    int *fallback = (fast && !will_emit) ? imp_knn::ensure(knn->fallback, batch) : nullptr;
-    int *counts = nullptr;  // tile maxima are refreshed after the filters: no slack for filtered entries is needed
-    const int extra = 0;
-
-    auto run = [&](const auto *Qb, const auto *Ib, auto Bf3c) {
-      using TQ = std::remove_cv_t<std::remove_pointer_t<decltype(Qb)>>;
-      using TI = std::remove_cv_t<std::remove_pointer_t<decltype(Ib)>>;
-      constexpr bool BF3 = decltype(Bf3c)::value;
-    // fp16 two-term planes for the resident-query kernels (topk_resident.h): the item matrix once per catalogue version (cached in
-    // the handle), the query rows of this call with one scale per row
-    const float *q_err_a = nullptr, *q_err_b = nullptr;
-    const unsigned *item_ne = nullptr;
-    const float *item_tile_n = nullptr;
-    auto prepare_planes = [&](int KS, const _Float16 *&iplanes, const int *&iexp, const _Float16 *&qplanes, const int *&qexp) {
-        IMP_PROF("split_query_rows");
-        auto &ip = knn->item_planes;
-        const size_t ni_pad = (ni + 127) / 128 * 128, F = (size_t)KS * 16;
-        const bool same = ip.key.src == items_in->data && ip.rows == ni && ip.cols == (size_t)f_in && ip.itemsize == items_in->itemsize && ip.KS == KS;
-        if (!same) {
-          ip.key.src = nullptr;
-          if (ip.planes.size < ni_pad * F * 2) ip.planes.alloc(ni_pad * F * 2);
-          if (ip.exp.size < 1) ip.exp.alloc(1), ip.maxbits.alloc(1), ip.ne.alloc(4);
-          if (ip.tile_n.size < ni_pad / 32) ip.tile_n.alloc(ni_pad / 32);
-          IMP_CHECK_HIP(hipMemsetAsync(ip.maxbits.data(), 0, sizeof(unsigned), stream()));
-          IMP_CHECK_HIP(hipMemsetAsync(ip.ne.data(), 0, 4 * sizeof(unsigned), stream()));
-          IMP_CHECK_HIP(hipMemsetAsync(ip.tile_n.data(), 0, (ni_pad / 32) * sizeof(unsigned), stream()));
-          const int g1 = (int)std::max<size_t>(1, std::min<size_t>((ni * (size_t)f + 255) / 256, (size_t)ctx().num_cus * 8));
-          rq_absmax_kernel<TI><<<g1, 256, 0, stream()>>>(Ib, ni * (size_t)f, ip.maxbits.data());
-          rq_item_exp_kernel<<<1, 1, 0, stream()>>>(ip.maxbits.data(), ip.exp.data());
-          const int g2 = (int)std::max<size_t>(1, std::min<size_t>((ni_pad * (F / 8) + 255) / 256, (size_t)ctx().num_cus * 16));
-          rq_split_items_kernel<TI><<<g2, 256, 0, stream()>>>(Ib, ip.planes.data(), ni, ni_pad, f, KS, ip.exp.data());
-          rq_item_err_kernel<TI><<<(int)std::min<size_t>((ni + 3) / 4, (size_t)ctx().num_cus * 16), 256, 0, stream()>>>(Ib, ni, f, ip.exp.data(),
-                                                                                                                    ip.ne.data(), ip.tile_n.data());
-          ip.rows = ni, ip.cols = (size_t)f_in, ip.itemsize = items_in->itemsize, ip.KS = KS;
-          const bool trusted = items_in->storage && items_in->storage->owned && !items_in->storage->exposed;
-          if (trusted) ip.key.src = items_in->data, ip.key.bytes = items_in->bytes();
-        }
-        iplanes = ip.planes.data(), iexp = ip.exp.data();
-        const size_t nq_pad = rq_query_pad(nq);
-        _Float16 *qp = imp_knn::ensure(knn->query_planes, nq_pad * F * 2);
-        int *qe = imp_knn::ensure(knn->query_exp, nq_pad);
-        float *qerr = imp_knn::ensure(knn->query_err, 2 * nq_pad);
-        rq_split_queries_kernel<TQ><<<(int)std::min<size_t>((nq_pad + 3) / 4, (size_t)ctx().num_cus * 8), 256, 0, stream()>>>(Qb, qp, qe, nq, nq_pad, f, KS,
-                                                                                                                             qerr, qerr + nq_pad);
-        IMP_CHECK_HIP(hipGetLastError());
-        qplanes = qp, qexp = qe;
-        q_err_a = qerr, q_err_b = qerr + nq_pad, item_ne = ip.ne.data(), item_tile_n = reinterpret_cast<const float *>(ip.tile_n.data());
-    };
-    static const bool resident_env = !(getenv("IMP_TOPK_RESIDENT") && atoi(getenv("IMP_TOPK_RESIDENT")) == 0);
-    constexpr bool bf16x3 = false;
-    // emit path (no score matrix): large item sets, k small against the candidate lists
-    static const bool no_emit = getenv("IMP_TOPK_NO_EMIT") != nullptr;
-    const bool emit_path = fast && !no_emit && emit_shape;
-    if (emit_path) {
-      const float *norms = item_norms ? item_norms->f32() : nullptr;
-      const int words = (int)((ni + 31) / 32);
-      const int n_blocks = (int)((ni + 127) / 128), n_sub = (n_blocks + stride - 1) / stride, sub_cols = n_sub * 128;
-      const size_t ebatch = std::min<size_t>(nq, 2048);
-      constexpr int FB = 64;  // fallback rows per materialised group
-      float *sub = imp_knn::ensure(knn->sub_scores, ebatch * (size_t)sub_cols);
-      uint32_t *tau = imp_knn::ensure(knn->tau, (ebatch + 127) / 128 * 128);  // the emit epilogue loads thresholds four rows at a time
-      unsigned int *cnt = imp_knn::ensure(knn->cand_count, ebatch);
-      uint64_t *cand = imp_knn::ensure(knn->cand, ebatch * (size_t)kEmitCap);
-      float *row_unscale = imp_knn::ensure(knn->row_unscale, rq_query_pad(ebatch));
-      int *fallback_e = host_flags;  // one flag per row of the batch, read by the host after the batch's wait
-      const bool have_coo = query_filter && query_filter->nnz, have_items = item_filter && item_filter->size;
-      if (have_coo && knn->row_bits.size < ebatch * (size_t)words) knn->row_bits_dirty = true;  // (regrown: fresh memory)
-      uint32_t *row_bits = have_coo ? imp_knn::ensure(knn->row_bits, ebatch * (size_t)words) : nullptr;
-      auto clear_row_bits = [&](size_t start, size_t end) {  // behind a batch: the words it set, back to zero
-        int grid = (int)std::min<size_t>(((size_t)query_filter->nnz + 255) / 256, (size_t)ctx().num_cus * 8);
-        coo_bitmap_clear_kernel<<<grid, 256, 0, stream()>>>(row_bits, words, (int)start, (int)end, (int)ni, query_filter->row.data(),
-                                                            query_filter->col.data(), (size_t)query_filter->nnz);
-        IMP_CHECK_HIP(hipGetLastError());
-        knn->row_bits_dirty = false;
-      };
-      uint32_t *item_bits = have_items ? imp_knn::ensure(knn->item_bits, (size_t)words) : nullptr;
-      if (have_items) IMP_CHECK_HIP(hipMemsetAsync(item_bits, 0, (size_t)words * 4, stream()));
-      static_assert(kFlagSlots >= 2048, "one flag per row of an emit batch");
-      const int *flags = host_flags;
-      std::vector<int32_t> fb_list;
-      constexpr bool no_qsplit = false;
-      constexpr bool kCanSplit = BF3;
-      const bool qsplit = kCanSplit && !no_qsplit;
-      // fp16 two-term form with the queries resident in registers and the item planes cached (topk_resident.h): every factor count
-      // that pads to 32 / 64 / 128 / 256; fp16-stored factors too (their values are their own high halves: scores stay bit-identical
-      // to scoring fp32 copies of them).  IMP_TOPK_RESIDENT=0: the six-product 128 x 128 kernel of rounds 3-4 (A/B, parity)
-      const int KS = rq_ks_for(f);
-      const bool resident = kCanSplit && resident_env && !bf16x3 && KS > 0;
-      split_bf16 *qs = nullptr;
-      const _Float16 *iplanes = nullptr, *qplanes = nullptr;
-      const int *iexp = nullptr, *qexp = nullptr;
-      if (resident) {
-        prepare_planes(KS, iplanes, iexp, qplanes, qexp);
-      } else if (qsplit) {
-        IMP_PROF("split_query_rows");
-        const size_t nq_pad = (nq + 127) / 128 * 128;  // whole 128-row query blocks: a workgroup reads all four tiles of its block
-        qs = imp_knn::ensure(knn->query_split, nq_pad * 3 * (size_t)f);
-        const int grid = (int)std::max<size_t>(1, std::min<size_t>((nq_pad * (size_t)f + 255) / 256, (size_t)ctx().num_cus * 16));
-        split_query_rows_kernel<TQ><<<grid, 256, 0, stream()>>>(Qb, reinterpret_cast<__bf16 *>(qs), nq, nq_pad, f);
-        IMP_CHECK_HIP(hipGetLastError());
-      }
-      // the two GEMM launches of a batch: query rows pre-split (default) or in their storage type
-      auto gemm = [&](auto mode_c, size_t start, dim3 grid, int rows, float *S_out, int bstride, const EmitArgs &ea) {
-        constexpr int M = decltype(mode_c)::value;
-        const float *norms_p = item_norms ? item_norms->f32() : nullptr;
-        if constexpr (kCanSplit) {
-          if (resident) {
-            ResidentArgs ra{};
-            ra.qsplit = qplanes + (start / 32) * (size_t)KS * 2 * 512;
-            ra.isplit = iplanes, ra.qexp = qexp + start, ra.iexp = iexp;
-            ra.nq = rows, ra.ni = (int)ni, ra.norms = norms_p;
-            ra.n_blocks = (int)grid.x, ra.block_stride = bstride;
-            ra.S = S_out, ra.sub_cols = (int)grid.x * 128, ra.emit = ea;
-            ra.qa = q_err_a ? q_err_a + start : nullptr, ra.qb = q_err_b ? q_err_b + start : nullptr, ra.ine = item_ne, ra.tile_n = item_tile_n;
-            launch_score_resident<M>(KS, ra, rows);
-            return;
-          }
-        }
-        if constexpr (M == 3) {
-          throw std::logic_error("the screened emit pass exists in the resident form only");
-        } else {
-          if constexpr (kCanSplit) {
-            if (qsplit) {
-              score_gemm_direct_kernel<M, split_bf16, TI, true><<<grid, 256, 0, stream()>>>(qs + start * 3 * (size_t)f, rows, Ib, (int)ni, f, norms_p,
-                                                                                      S_out, nullptr, 0, bstride, ea);
-              return;
-            }
-          }
-          score_gemm_direct_kernel<M, TQ, TI, BF3><<<grid, 256, 0, stream()>>>(Qb + start * f, rows, Ib, (int)ni, f, norms_p, S_out, nullptr, 0,
-                                                                              bstride, ea);
-        }
-      };
-      // screened emit pass (topk_resident.h MODE 3): one-product scores against tau - eps, the few candidates that can still be among
-      // the best k re-scored in fp32 by the select kernel.  Dot-product scores only (no item norms); IMP_TOPK_SCREEN=0: three products
-      static const bool screen_env = !(getenv("IMP_TOPK_SCREEN") && atoi(getenv("IMP_TOPK_SCREEN")) == 0);
-      const bool screen = resident && screen_env && !item_norms;
-      float *row_eps = screen ? imp_knn::ensure(knn->row_eps, rq_query_pad(ebatch)) : nullptr;
-      for (size_t start = 0; start < nq; start += ebatch) {
-        const size_t end = std::min(nq, start + ebatch), rows = end - start;
-        const auto *qptr = Qb + start * f;
-        const unsigned qblocks = (unsigned)((rows + 127) / 128);
-        if (have_coo) {
-          if (knn->row_bits_dirty) IMP_CHECK_HIP(hipMemsetAsync(row_bits, 0, knn->row_bits.size * sizeof(uint32_t), stream()));
-          knn->row_bits_dirty = true;  // (until this batch's clear is queued)
-        }
-        {
-          IMP_PROF("score_gemm_subset");
-          gemm(std::integral_constant<int, 1>{}, start, dim3((unsigned)n_sub, qblocks), (int)rows, sub, stride, EmitArgs{});
-          IMP_CHECK_HIP(hipGetLastError());
-        }
-        if (have_items) {
-          IMP_PROF("item_filter");
-          int grid = (int)std::min<size_t>((item_filter->size + 255) / 256, (size_t)ctx().num_cus * 8);
-          item_bitmap_kernel<<<grid, 256, 0, stream()>>>(item_bits, (int)ni, item_filter->v.data(), (int)item_filter->size, sub, (int)rows,
-                                                         sub_cols, stride);
-          IMP_CHECK_HIP(hipGetLastError());
-        }
-        if (have_coo) {
-          IMP_PROF("coo_filter");
-          int grid = (int)std::min<size_t>(((size_t)query_filter->nnz + 255) / 256, (size_t)ctx().num_cus * 8);
-          coo_bitmap_kernel<<<grid, 256, 0, stream()>>>(row_bits, words, (int)start, (int)end, (int)ni, query_filter->row.data(),
-                                                        query_filter->col.data(), (size_t)query_filter->nnz, sub, sub_cols, stride);
-          IMP_CHECK_HIP(hipGetLastError());
-        }
-        {
-          IMP_PROF("topk_threshold");
-          if (k_eff <= 32)
-            subset_threshold_groupmax_kernel<256><<<(unsigned)rows, 256, 0, stream()>>>(sub, sub_cols, k_eff, tau, cnt);
-          else
-            subset_threshold_kernel<512><<<(unsigned)rows, 512, 0, stream()>>>(sub, sub_cols, k_eff, tau, cnt);
-          IMP_CHECK_HIP(hipGetLastError());
-        }
-        {
-          IMP_PROF("score_gemm");
-          EmitArgs ea{tau, row_bits, item_bits, words, cand, cnt, kEmitCap, resident ? row_unscale : nullptr, row_eps};
-          if (screen) gemm(std::integral_constant<int, 3>{}, start, dim3((unsigned)n_blocks, qblocks), (int)rows, nullptr, 1, ea);
-          else gemm(std::integral_constant<int, 2>{}, start, dim3((unsigned)n_blocks, qblocks), (int)rows, nullptr, 1, ea);
-          IMP_CHECK_HIP(hipGetLastError());
-        }
-        {
-          IMP_PROF("topk_select_candidates");
-          if (screen)
-            select_screened_kernel<512, TQ, TI><<<(unsigned)rows, 512, 0, stream()>>>(cand, cnt, kEmitCap, k_eff, d_ids + start * k, d_dist + start * k, k,
-                                                                                     fallback_e, row_eps, Qb + start * f, Ib, f, host_counts);
-          else
-            select_candidates_kernel<512><<<(unsigned)rows, 512, 0, stream()>>>(cand, cnt, kEmitCap, k_eff, d_ids + start * k,
-                                                                               d_dist + start * k, k, fallback_e, resident ? row_unscale : nullptr);
-          IMP_CHECK_HIP(hipGetLastError());
-#ifdef RQ_SCREEN_STATS
-          if (screen) {
-            unsigned long long h[4];
-            IMP_CHECK_HIP(hipStreamSynchronize(stream()));
-            IMP_CHECK_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(rq_screen_stats), sizeof(h)));
-            fprintf(stderr, "[screen-stats] rows %llu, candidates per row %.1f, re-scored per row %.1f (largest so far: %llu)\n", h[0],
-                    (double)h[1] / std::max(1ull, h[0]), (double)h[2] / std::max(1ull, h[0]), h[3]);
-          }
-#endif
-        }
-        sync();
-        fb_list.clear();
-        for (size_t i = 0; i < rows; ++i)
-          if (flags[i]) fb_list.push_back((int32_t)i);
-        if (screen && fb_list.size() * 8 > rows) {
-          // The screen separated nothing for much of this batch: scores so concentrated that an 11-bit product cannot tell the
-          // best k from the bulk (factors a sweep or two from an all-positive start: every score within 1e-3 of the next) -- the
-          // lists overflowed.  The WHOLE batch is redone by the three-product emit pass with its exact threshold test (same
-          // thresholds, lists reset) before anything goes to the row-by-row exact path: 0.25 ms per 1000 rows instead of 1.3.
-          // Decided by this batch's own outcome, not by the handle's history: the same call gives the same bits every time.
-          IMP_PROF("topk_exact_emit_retry");
-          IMP_CHECK_HIP(hipMemsetAsync(cnt, 0, rows * sizeof(unsigned int), stream()));
-          EmitArgs ea{tau, row_bits, item_bits, words, cand, cnt, kEmitCap, row_unscale, nullptr};
-          gemm(std::integral_constant<int, 2>{}, start, dim3((unsigned)n_blocks, qblocks), (int)rows, nullptr, 1, ea);
-          select_candidates_kernel<512><<<(unsigned)rows, 512, 0, stream()>>>(cand, cnt, kEmitCap, k_eff, d_ids + start * k, d_dist + start * k, k,
-                                                                             fallback_e, row_unscale);
-          IMP_CHECK_HIP(hipGetLastError());
-          sync();
-          fb_list.clear();
-          for (size_t i = 0; i < rows; ++i)
-            if (flags[i]) fb_list.push_back((int32_t)i);
-        }
-        if (screen && rows >= 64) {  // the stride rule (above): mean list length and exact-path rows of this batch
-          size_t total = 0;
-          for (size_t i = 0; i < rows; ++i) total += (size_t)host_counts[i];
-          const size_t mean = total / rows;
-          if (fb_list.size() * 100 > rows || mean > 400) knn->stride_boost = std::max(1, knn->stride_boost / 2);
-          else if (mean < 48 && knn->stride_boost < 4) knn->stride_boost *= 2;
-        }
-        static const bool debug = getenv("IMP_TOPK_DEBUG") != nullptr;
-        if (debug && !fb_list.empty()) {
-          std::vector<unsigned int> hc(rows);
-          std::vector<uint32_t> ht(rows);
-          IMP_CHECK_HIP(hipMemcpy(hc.data(), cnt, rows * 4, hipMemcpyDeviceToHost));
-          IMP_CHECK_HIP(hipMemcpy(ht.data(), tau, rows * 4, hipMemcpyDeviceToHost));
-          fprintf(stderr, "[topk-debug] batch at %zu: %zu fallback rows:", start, fb_list.size());
-          for (size_t i = 0; i < std::min<size_t>(fb_list.size(), 8); ++i)
-            fprintf(stderr, " (row %d count %u tau-key %08x)", fb_list[i], hc[fb_list[i]], ht[fb_list[i]]);
-          fprintf(stderr, "\n");
-        }
-        if (!fb_list.empty()) {  // overflow / short list / exact tie at the k-th score: the materialising path, FB rows at a time
-          IMP_PROF("topk_fallback");
-          int32_t *d_rows = imp_knn::ensure(knn->fb_rows, fb_list.size());
-          IMP_CHECK_HIP(hipMemcpyAsync(d_rows, fb_list.data(), fb_list.size() * 4, hipMemcpyHostToDevice, stream()));
-          float *fbq = imp_knn::ensure(knn->fb_query, (size_t)FB * f);
-          float *fscores = imp_knn::ensure(knn->scores, (size_t)FB * ni);
-          float *ftile = imp_knn::ensure(knn->tile_max, (size_t)FB * n_tiles);
-          int32_t *fids = imp_knn::ensure(knn->fb_ids, (size_t)FB * k);
-          float *fdist = imp_knn::ensure(knn->fb_dist, (size_t)FB * k);
-          uint64_t *fg = use_lds ? nullptr : imp_knn::ensure(knn->gcand, (size_t)FB * kpad);
-          const size_t lds = use_lds ? (size_t)kpad * 8 : 0;
-          auto kern = select_kernel<512>;
-          IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)std::max<size_t>(lds, 1)));
-          for (size_t g0 = 0; g0 < fb_list.size(); g0 += FB) {
-            const int n = (int)std::min<size_t>(FB, fb_list.size() - g0);
-            gather_query_rows_kernel<TQ><<<std::max(1, (n * f + 255) / 256), 256, 0, stream()>>>(qptr, d_rows + g0, n, f, fbq);
-            score_gemm_direct_kernel<0, float, TI, BF3><<<dim3((unsigned)n_blocks, 1), 256, 0, stream()>>>(fbq, n, Ib, (int)ni, f, norms, fscores,
-                                                                                         ftile, n_tiles, 1, EmitArgs{});
-            if (have_coo || have_items) {
-              int grid = (int)std::min<size_t>(((size_t)n * n_tiles + 255) / 256, (size_t)ctx().num_cus * 8);
-              bitmap_filter_kernel<<<grid, 256, 0, stream()>>>(fscores, ftile, (int)ni, n_tiles, d_rows + g0, n, row_bits, item_bits, words);
-            }
-            kern<<<(unsigned)n, 512, lds, stream()>>>(fscores, (int)ni, k_eff, kpad, fids, fdist, k, fg, use_lds ? 1 : 0, nullptr);
-            scatter_topk_rows_kernel<<<std::max(1, (n * k + 255) / 256), 256, 0, stream()>>>(fids, fdist, d_rows + g0, n, k,
-                                                                                         d_ids + start * k, d_dist + start * k);
-            IMP_CHECK_HIP(hipGetLastError());
-          }
-        }
-        if (have_coo && end < nq) clear_row_bits(start, end);  // (the last batch's: behind the call's wait, below)
-      }
-      deliver();
-      if (have_coo && nq > 0) clear_row_bits((nq - 1) / ebatch * ebatch, nq);
-      return;
-    }
-
-    const int KS0 = rq_ks_for(f);
-    const bool resident0 = BF3 && fast && resident_env && !bf16x3 && KS0 > 0;
-    const _Float16 *iplanes0 = nullptr, *qplanes0 = nullptr;
-    const int *iexp0 = nullptr, *qexp0 = nullptr;
-    if (resident0) prepare_planes(KS0, iplanes0, iexp0, qplanes0, qexp0);
-    for (size_t start = 0; start < nq; start += batch) {
-      size_t end = std::min(nq, start + batch), rows = end - start;
-      bool filters_applied = false;
-      if (resident0) {
-        IMP_PROF("score_gemm");
-        ResidentArgs ra{};
-        ra.qsplit = qplanes0 + (start / 32) * (size_t)KS0 * 2 * 512;
-        ra.isplit = iplanes0, ra.qexp = qexp0 + start, ra.iexp = iexp0;
-        ra.nq = (int)rows, ra.ni = (int)ni, ra.norms = item_norms ? item_norms->f32() : nullptr;
-        ra.n_blocks = (int)((ni + 127) / 128), ra.block_stride = 1;
-        ra.S = scores, ra.tile_max = tile_max, ra.n_tiles64 = n_tiles;
-        launch_score_resident<0>(KS0, ra, (int)rows);
-      } else if (fast) {
-        IMP_PROF("score_gemm");
-        dim3 grid((unsigned)((ni + 127) / 128), (unsigned)((rows + 127) / 128));
-        score_gemm_direct_kernel<0, TQ, TI, BF3><<<grid, 256, 0, stream()>>>(Qb + start * f, (int)rows, Ib, (int)ni, f,
-                                                                item_norms ? item_norms->f32() : nullptr, scores, tile_max,
-                                                                n_tiles, 1, EmitArgs{});
-        IMP_CHECK_HIP(hipGetLastError());
-      } else {
-        IMP_PROF("score_gemm_lds");
-        dim3 grid((unsigned)((ni + kBN - 1) / kBN), (unsigned)((rows + kBM - 1) / kBM));
-        if constexpr (std::is_same<TQ, float>::value) {  // the general path always runs on fp32 (copies of fp16 factors)
-          score_gemm_kernel<<<grid, 256, 0, stream()>>>(Qb + start * f, (int)rows, Ib, (int)ni, f,
-                                                        item_norms ? item_norms->f32() : nullptr, scores);
-          IMP_CHECK_HIP(hipGetLastError());
-        }
-      }
-      if (item_filter && item_filter->size) {
-        IMP_PROF("item_filter");
-        size_t total = rows * item_filter->size;
-        int grid = (int)std::min<size_t>((total + 255) / 256, (size_t)ctx().num_cus * 8);
-        item_filter_kernel<<<grid, 256, 0, stream()>>>(scores, (int)rows, (int)ni, item_filter->v.data(), (int)item_filter->size);
-        IMP_CHECK_HIP(hipGetLastError());
-        filters_applied = true;
-      }
-      if (query_filter && query_filter->nnz) {
-        IMP_PROF("coo_filter");
-        int grid = (int)std::min<size_t>(((size_t)query_filter->nnz + 255) / 256, (size_t)ctx().num_cus * 8);
-        coo_filter_kernel<<<grid, 256, 0, stream()>>>(scores, (int)start, (int)end, (int)ni, query_filter->row.data(),
-                                                      query_filter->col.data(), (size_t)query_filter->nnz);
-        IMP_CHECK_HIP(hipGetLastError());
-        filters_applied = true;
-      }
-      if (fast && filters_applied) {
-        // second phase (all filter writes are done): refresh the maxima of the touched tiles
-        IMP_PROF("filter_tile_refresh");
-        if (item_filter && item_filter->size) {
-          size_t total = rows * item_filter->size;
-          int grid = (int)std::min<size_t>((total + 255) / 256, (size_t)ctx().num_cus * 8);
-          item_filter_refresh_kernel<<<grid, 256, 0, stream()>>>(scores, tile_max, (int)rows, (int)ni, n_tiles,
-                                                                 item_filter->v.data(), (int)item_filter->size);
-        }
-        if (query_filter && query_filter->nnz) {
-          int grid = (int)std::min<size_t>(((size_t)query_filter->nnz + 255) / 256, (size_t)ctx().num_cus * 8);
-          coo_filter_refresh_kernel<<<grid, 256, 0, stream()>>>(scores, tile_max, (int)start, (int)end, (int)ni, n_tiles,
-                                                                query_filter->row.data(), query_filter->col.data(),
-                                                                (size_t)query_filter->nnz);
-        }
-        IMP_CHECK_HIP(hipGetLastError());
-      }
-      if (fast) {
-        IMP_PROF("topk_select_pruned");
-        select_pruned_kernel<512><<<(unsigned)rows, 512, 0, stream()>>>(scores, tile_max, (int)ni, n_tiles, k_eff, extra, counts,
-                                                                       d_ids + start * k, d_dist + start * k, k, fallback);
-        IMP_CHECK_HIP(hipGetLastError());
-      }
-      {
-        IMP_PROF("topk_select");
-        size_t lds = use_lds ? (size_t)kpad * 8 : 0;
-        auto kern = select_kernel<512>;
-        IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)std::max<size_t>(lds, 1)));
-        kern<<<(unsigned)rows, 512, lds, stream()>>>(scores, (int)ni, k_eff, kpad, d_ids + start * k, d_dist + start * k, k, gcand,
-                                                     use_lds ? 1 : 0, fast ? fallback : nullptr);
-        IMP_CHECK_HIP(hipGetLastError());
-      }
-      static const bool debug_m = getenv("IMP_TOPK_DEBUG") != nullptr;
-      if (debug_m && fast) {  // how many rows the pruned select handed to the exact select
-        std::vector<int> hf(rows);
-        IMP_CHECK_HIP(hipMemcpy(hf.data(), fallback, rows * sizeof(int), hipMemcpyDeviceToHost));
-        size_t nfb = 0, first_fb = 0;
-        for (size_t i = 0; i < rows; ++i)
-          if (hf[i]) {
-            if (!nfb) first_fb = i;
-            ++nfb;
-          }
-        fprintf(stderr, "[topk-debug] materialising batch at %zu: %zu of %zu rows re-done by the exact select (first: row %zu)\n", start, nfb,
-                rows, first_fb);
-      }
-    }
-    deliver();
-    };
-    // IMP_TOPK_FP32_MFMA=1: the exact-fp32 MFMA form (v_mfma_f32_32x32x2_f32) instead of the split-bf16 one (A/B, parity)
-    static const bool exact_mfma = getenv("IMP_TOPK_FP32_MFMA") != nullptr;
-    const bool bf3 = fast && !exact_mfma && f % 16 == 0;
-    if (half_direct) {
-      const __half *qh = reinterpret_cast<const __half *>(query_in->data), *ih = reinterpret_cast<const __half *>(items_in->data);
-      if (bf3) run(qh, ih, std::true_type{});
-      else run(qh, ih, std::false_type{});
-    } else if (bf3) {
-      run(query->f32(), items->f32(), std::true_type{});
-    } else {
-      run(query->f32(), items->f32(), std::false_type{});
-    }
+    const OutputStage out = stage_outputs(knn, nq, k, k_eff, indices, distances);
+    const int stride = emit_stride(knn, ni, k_eff, item_norms != nullptr);
+    const TopkCall c{knn, items_in, nq, ni, f, k, k_eff, kpad, fast, (size_t)kpad * 8 <= 96 * 1024, stride,
+                     (int)((ni + kTileItems - 1) / kTileItems), item_norms ? item_norms->f32() : nullptr,
+                     query_filter && query_filter->nnz ? query_filter : nullptr, item_filter && item_filter->size ? item_filter : nullptr, out};
+    // ONE predicate decides both what is allocated (the emit route has no score matrix) and what runs
+    const bool emit = fast && sw.emit && k_eff == k && k_eff <= 256 && stride >= 8;
+    // split-bf16 / two-term forms need f on the 16-grid -- and every f of the fast path is: one that is not was padded above
+    const bool bf3 = fast && !sw.exact_mfma;
+    if (op.half) bf3 ? topk_route<__half, true>(c, emit, op) : topk_route<__half, false>(c, emit, op);
+    else bf3 ? topk_route<float, true>(c, emit, op) : topk_route<float, false>(c, emit, op);
   });
 }
 
