@@ -8,7 +8,8 @@ released (ctypes.CDLL does that), as the reference does with `with nogil` (_cuda
 
 NEW relative to the reference: LeastSquaresSolver.least_squares_cholesky (the reference GPU path
 has no Cholesky solver), the Comm class (RCCL exchange for the multi-GPU fit), lmf_update (the
-reference has no GPU LMF) and SpMat / sparse_topk_product (the reference's nearest-neighbour models are CPU only).
+reference has no GPU LMF), SpMat / sparse_topk_product (the reference's nearest-neighbour models are CPU only) and IVFIndex
+(a native IVF-Flat index in place of the faiss one the reference's ann wrappers build).
 """
 import ctypes
 
@@ -551,6 +552,97 @@ def host_ranking_metrics(test_user_items, K, ids, userids, per_row=False):
                                          _vp(userids), len(userids), _vp(sums), _vp(out) if per_row else None))
     sums = dict(zip(_SUM_NAMES, sums.tolist()))
     return (sums, out) if per_row else sums
+
+
+class IVFIndex:
+    """NEW: a native IVF-Flat index over the rows of a factor matrix (imp_ivf, csrc/ivf.hip) -- what the reference builds
+    with faiss.GpuIndexIVFFlat (implicit/ann/faiss.py).  Build it with IVFIndex.build; search returns, per query, the k best
+    vectors among the `nprobe` lists whose centroids are nearest by inner product."""
+
+    def __init__(self):
+        self._h = ctypes.c_void_p()
+
+    @classmethod
+    def build(cls, vectors, nlist, iterations=10, init_rows=None, random_state=None, max_temp_memory=0):
+        """vectors: a Matrix or a float32 / float16 array (rows x factors, 1 .. 1024 factors; the index stores fp32).
+        init_rows: the `nlist` distinct rows the centroids start from; by default drawn without replacement from
+        numpy.random.default_rng(random_state).  iterations: rounds of spherical k-means.  max_temp_memory: bytes of
+        temporaries of one chunk of queries, 0 = min(free / 2, 4 GiB) as KnnQuery.  Deterministic for equal arguments."""
+        if not isinstance(vectors, Matrix):
+            vectors = Matrix(vectors)
+        nlist = int(nlist)
+        rows = vectors.shape[0]
+        if not 1 <= nlist <= rows:
+            raise ValueError("IVFIndex.build: nlist must lie in 1 .. rows")
+        if init_rows is None:
+            init_rows = np.random.default_rng(random_state).choice(rows, size=nlist, replace=False)
+        init_rows = np.ascontiguousarray(init_rows, dtype=np.int32)
+        if init_rows.shape != (nlist,):
+            raise ValueError("IVFIndex.build: init_rows must hold nlist row ids")
+        self = cls()
+        check(lib().imp_ivf_build(vectors._h, nlist, int(iterations), _vp(init_rows), ctypes.byref(self._h)))
+        if max_temp_memory:
+            check(lib().imp_ivf_set_temp_memory(self._h, int(max_temp_memory)))
+        return self
+
+    def set_temp_memory(self, max_temp_memory=0):
+        check(lib().imp_ivf_set_temp_memory(self._h, int(max_temp_memory)))
+
+    def _shape(self):
+        r, c, n = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int()
+        check(lib().imp_ivf_shape(self._h, ctypes.byref(r), ctypes.byref(c), ctypes.byref(n)))
+        return r.value, c.value, n.value
+
+    @property
+    def shape(self):
+        return self._shape()[:2]
+
+    @property
+    def nlist(self):
+        return self._shape()[2]
+
+    @property
+    def centroids(self):
+        """nlist x factors float32: unit rows, or zero rows."""
+        _, c, n = self._shape()
+        out = np.empty((n, c), dtype=np.float32)
+        check(lib().imp_ivf_lists(self._h, _vp(out), None, None))
+        return out
+
+    @property
+    def list_offsets(self):
+        out = np.empty(self.nlist + 1, dtype=np.int64)
+        check(lib().imp_ivf_lists(self._h, None, _vp(out), None))
+        return out
+
+    @property
+    def list_ids(self):
+        """The row ids list by list: list l is list_ids[list_offsets[l]:list_offsets[l + 1]], ascending."""
+        out = np.empty(self.shape[0], dtype=np.int32)
+        check(lib().imp_ivf_lists(self._h, None, None, _vp(out)))
+        return out
+
+    def search(self, queries, k, nprobe, return_probes=False):
+        """(ids int32, scores float32), each queries x k, best first under (score desc, id desc); where the probed lists hold
+        fewer than k vectors the tail is (-1, -FLT_MAX).  nprobe above nlist is nlist.  return_probes adds the
+        queries x min(nprobe, nlist) probed list ids.  k outside 1 .. 1024 or nprobe < 1 raise ValueError."""
+        if not isinstance(queries, Matrix):
+            queries = Matrix(queries)
+        k, nprobe = int(k), int(nprobe)
+        if k < 1 or nprobe < 1:
+            raise ValueError("IVFIndex.search: k and nprobe must be >= 1")
+        rows = queries.shape[0]
+        ids = np.empty((rows, k), dtype=np.int32)
+        dist = np.empty((rows, k), dtype=np.float32)
+        probes = np.empty((rows, min(nprobe, self.nlist)), dtype=np.int32) if return_probes else None
+        check(lib().imp_ivf_search(self._h, queries._h, k, min(nprobe, 2**31 - 1), _vp(ids), _vp(dist),
+                                   _vp(probes) if return_probes else None))
+        return (ids, dist, probes) if return_probes else (ids, dist)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().imp_ivf_destroy(self._h)
+            self._h = None
 
 
 class Comm:

@@ -106,6 +106,14 @@ _SIGNATURES = {
     "imp_host_ranking_metrics": [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                  ctypes.c_void_p, ctypes.c_void_p],
+    "imp_ivf_build": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_void_pp],
+    "imp_ivf_shape": [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+                      ctypes.POINTER(ctypes.c_int)],
+    "imp_ivf_set_temp_memory": [ctypes.c_void_p, ctypes.c_size_t],
+    "imp_ivf_lists": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    "imp_ivf_search": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p],
+    "imp_ivf_destroy": [ctypes.c_void_p],
     "imp_comm_unique_id": [ctypes.c_void_p],
     "imp_comm_init_rank": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_void_pp],
     "imp_comm_destroy": [ctypes.c_void_p],

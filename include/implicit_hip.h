@@ -288,6 +288,32 @@ int imp_host_ranking_metrics(int32_t rows, int32_t cols, const void *indptr, int
                              const double *cg, const double *cg_sum, const int32_t *ids, const int32_t *userids, int64_t n,
                              double *sums, double *per_row);
 
+/* ---- NEW: IVF-Flat approximate nearest neighbours (reference: the faiss.GpuIndexIVFFlat the wrappers of implicit/ann/faiss.py
+ * build; here a native index, csrc/ivf.hip) ------------------------------------------------------------------------------- */
+typedef struct imp_ivf imp_ivf; /* centroids + inverted lists of fp32 vectors, device-resident */
+/* Builds the index over the rows of `vectors` (fp32 or fp16, widened; 1 .. 1024 columns) on the device: the centroids start
+ * as the unit-normalised rows init_rows[0 .. nlist) (a zero row stays zero); `iterations` rounds of spherical k-means follow
+ * -- every vector goes to the centroid of largest inner product, ties to the larger list id; every centroid becomes the
+ * normalised mean of its list, summed in ascending vector id, an empty list or a zero mean keeping the old centroid -- and
+ * the lists are rebuilt against the final centroids.  Deterministic.  IMP_INVALID_ARGUMENT: nlist outside 1 .. rows,
+ * iterations < 0, a column count outside 1 .. 1024; IMP_OUT_OF_RANGE: an initial row id outside the matrix. */
+int imp_ivf_build(const imp_matrix *vectors, int nlist, int iterations, const int32_t *init_rows, imp_ivf **out);
+int imp_ivf_shape(const imp_ivf *ix, size_t *rows, size_t *cols, int *nlist);
+/* Bytes of temporaries one chunk of queries of a search may take; 0 restores the default min(free / 2, 4 GiB) of KnnQuery.
+ * The index keeps the temporaries of its last search for the next one; this call frees them. */
+int imp_ivf_set_temp_memory(imp_ivf *ix, size_t max_temp_memory);
+/* HOST outputs, each nullable: centroids[nlist x cols], list_offsets[nlist + 1], list_ids[rows] (list l holds the vectors
+ * list_ids[list_offsets[l] .. list_offsets[l + 1]), ascending). */
+int imp_ivf_lists(const imp_ivf *ix, float *centroids, int64_t *list_offsets, int32_t *list_ids);
+/* The k best vectors of each query (fp32 or fp16, the index's column count) among the P = min(nprobe, nlist) lists whose
+ * centroids have the largest inner product with it.  indices / distances: [query.rows x k], host or device, best first in the
+ * total order (score desc, id desc), scores exact fp32 fmaf chains over the columns in order; where the probed lists hold
+ * fewer than k vectors the tail is id -1, score -FLT_MAX.  probes (nullable): [query.rows x P], the probed lists, best first
+ * (score desc, list id desc).  Queries are processed in chunks that fit the temporary budget; the chunking changes no
+ * result.  IMP_INVALID_ARGUMENT: k outside 1 .. 1024, nprobe < 1, P > 1024, a column count that differs. */
+int imp_ivf_search(imp_ivf *ix, const imp_matrix *query, int k, int nprobe, int32_t *indices, float *distances, int32_t *probes);
+int imp_ivf_destroy(imp_ivf *ix);
+
 /* ---- NEW: multi-GPU exchange over RCCL / xGMI (no reference counterpart) ------------------------ */
 /* One process per GPU.  Rank 0 calls imp_comm_unique_id, the host side broadcasts the 128 bytes by
  * any means (torch.distributed store, MPI, a file) and every rank calls imp_comm_init_rank. */
