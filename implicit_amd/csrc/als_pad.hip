@@ -53,6 +53,9 @@ PaddedViews pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *Y
   PaddedSystem &p = ctx().pad;
   const size_t rx = rows_of_X, ry = Y->rows;
   if (p.x.size < rx * F) p.x.alloc(rx * F);
+  // no copy is kept of memory whose writes the library does not see -- wrapped foreign memory, a matrix whose address was handed
+  // out (the predicate of the cached item planes, topk.hip)
+  if (!(Y->storage && Y->storage->owned && !Y->storage->exposed)) reuse_y = false;
   // a copy that may not be re-used, or that goes with its buffer, is forgotten (before the alloc: freeing the buffer reports a
   // write to that memory)
   if (!reuse_y || p.y.size < ry * F) p.forget_y();
@@ -67,6 +70,7 @@ PaddedViews pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *Y
     // was made under vouches for it.  The flag is read by the pad kernel itself, which then returns at once.
     const int *skip = nullptr;
     if (ry && p.y_src == Y->data && p.y_rows == ry && p.y_f == f && p.y_F == F) {
+      IMP_PROF_NESTED("padded_y_check");  // one count per call that found a kept copy to vouch for: what the cache tests read
       if (p.same.size < 1) p.same.alloc(1);
       pad_check_kernel<<<1, 1024, 0, stream()>>>(YtY->f32(), p.gram.data(), f, F, p.same.data());
       skip = p.same.data();

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -113,6 +114,15 @@ struct ProfScope {
 bool prof_enabled();
 bool prof_unfiltered();  // on, and with no name filter: every scope is timed (a per-kernel pass such as bench.py --full's)
 #define IMP_PROF(name) ::imp::ProfScope _prof_scope_(name)
+// A scope INSIDE another one (a count of its own for part of what the outer scope times): recorded only when a name filter is
+// set -- an unfiltered per-kernel pass adds the scopes up and would count its time twice.
+struct NestedProfScope {
+  std::optional<ProfScope> scope;
+  explicit NestedProfScope(const char *name) {
+    if (prof_enabled() && !prof_unfiltered()) scope.emplace(name);
+  }
+};
+#define IMP_PROF_NESTED(name) ::imp::NestedProfScope _prof_nested_(name)
 
 // ---- device storage ---------------------------------------------------------------------------
 struct Context;
@@ -220,7 +230,8 @@ void note_device_write(const void *dst, size_t bytes);
 // Something derived from device memory the library owns and kept across calls (the fragment-ordered fp16 planes of an item
 // matrix in a KnnQuery handle, topk.hip): `src` / `bytes` name what it was made from; note_device_write clears `src` of every
 // registered cache the written range overlaps.  Holds for memory only the library writes: a Storage whose address was handed
-// out (imp_matrix_device_ptr) or that wraps foreign memory (imp_matrix_wrap_device) is `exposed` and never cached from.
+// out (imp_matrix_device_ptr) or that wraps foreign memory (imp_matrix_wrap_device) is never cached from: handing the address
+// out counts as a write, and neither a cache hit nor a kept padded copy of Y is taken from such memory afterwards.
 struct DerivedCache {
   const void *src = nullptr;
   size_t bytes = 0;

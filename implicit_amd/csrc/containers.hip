@@ -787,7 +787,10 @@ int imp_matrix_shape(const imp_matrix *m, size_t *rows, size_t *cols, size_t *it
 int imp_matrix_device_ptr(const imp_matrix *m, void **ptr) {
   return guarded([&] {
     *ptr = m->data;
-    if (m->storage) m->storage->exposed = true;  // whoever holds the address may write through it: nothing derived from this memory is cached
+    // whoever holds the address may write through it: nothing derived from this memory is cached from now on, and what was
+    // derived from it before is dropped
+    if (m->storage) m->storage->exposed = true;
+    note_device_write(m->data, m->bytes());
   });
 }
 

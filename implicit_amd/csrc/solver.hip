@@ -214,6 +214,9 @@ int imp_solver_least_squares(imp_solver *, const imp_csr *cui, imp_matrix *X, co
   return guarded([&] {
     check_solver_args(cui, X, YtY, Y);
     if (cg_steps < 0) throw std::invalid_argument("cg_steps must be >= 0");
+    // the rows this call solves, in the CALLER's matrix: least_squares_cg reports the write on the matrix it is handed, which for
+    // fp16 factors outside the native factor counts is an fp32 temporary (run_with_f32 copies the result back)
+    note_device_write(X->data, (size_t)cui->rows * X->cols * X->itemsize);
     auto body = [&](imp_matrix *x, const imp_matrix *y) {
       for_each_part(cui, x, [&](const imp_csr *part, const imp_matrix *xp) {
         least_squares_cg(part, const_cast<imp_matrix *>(xp), YtY, y, cg_steps);

@@ -1546,8 +1546,11 @@ template <typename TQ, typename TI> static ResidentArgs split_planes(const TopkC
   const size_t nq = c.nq, ni = c.ni, ni_pad = (ni + 127) / 128 * 128, F = (size_t)KS * 16;
   const int f = c.f;
   auto &ip = c.knn->item_planes;
-  const bool same = ip.key.src == items_in->data && ip.rows == ni && ip.cols == items_in->cols && ip.itemsize == items_in->itemsize && ip.KS == KS;
+  // memory the library cannot vouch for never hits, whatever the key says (the address may have been handed out after the planes were made)
+  const bool trusted = items_in->storage && items_in->storage->owned && !items_in->storage->exposed;
+  const bool same = trusted && ip.key.src == items_in->data && ip.rows == ni && ip.cols == items_in->cols && ip.itemsize == items_in->itemsize && ip.KS == KS;
   if (!same) {
+    IMP_PROF_NESTED("item_planes_split");  // one count per (re)build of the item planes: what the cache tests read
     ip.key.src = nullptr;
     if (ip.planes.size < ni_pad * F * 2) ip.planes.alloc(ni_pad * F * 2);
     if (ip.exp.size < 1) ip.exp.alloc(1), ip.maxbits.alloc(1), ip.ne.alloc(4);
@@ -1561,7 +1564,6 @@ template <typename TQ, typename TI> static ResidentArgs split_planes(const TopkC
     rq_item_err_kernel<TI><<<(int)std::min<size_t>((ni + 3) / 4, (size_t)ctx().num_cus * 16), 256, 0, stream()>>>(Ib, ni, f, ip.exp.data(),
                                                                                                               ip.ne.data(), ip.tile_n.data());
     ip.rows = ni, ip.cols = items_in->cols, ip.itemsize = items_in->itemsize, ip.KS = KS;
-    const bool trusted = items_in->storage && items_in->storage->owned && !items_in->storage->exposed;
     if (trusted) ip.key.src = items_in->data, ip.key.bytes = items_in->bytes();
   }
   const size_t nq_pad = rq_query_pad(nq);

@@ -346,7 +346,8 @@ def test_more_than_1024_factors_is_an_error_like_the_reference(gpu):
 def test_padded_copy_of_y_is_reused_only_while_it_is_valid(gpu, oracle):
     """f = 100 rides the f = 128 kernels on a zero-padded copy of Y.  The row chunks of a half sweep solve against the same Y
     under the same gramian: the copy is made once (decided on the device through the gramian, als_cg.hip).  It must NOT
-    survive a write to Y through the library, nor a different gramian."""
+    survive a write to Y through the library, nor a different gramian.  (Every other writer of Y, and memory the library cannot
+    watch: tests/test_gpu_derived_state.py.)"""
     f = 100
     C = synthetic_csr(2400, 900, 60_000, seed=41, neg_frac=0.05, empty_frac=0.02)
     rng = np.random.default_rng(5)

@@ -335,7 +335,8 @@ def test_fp16_form_with_outlier_item_rows(gpu, oracle):
 def test_item_plane_cache_follows_writes(gpu, oracle):
     """The fragment-ordered fp16 planes of the item matrix live in the KnnQuery handle across calls (topk_resident.h).  Every write
     to the matrix through the library must invalidate them: a host upload, assign_rows, a solver sweep over the rows.  A matrix
-    whose device address was handed out is never cached from."""
+    whose device address was handed out is never cached from.  (The whole table of writers against derived state, other types and
+    factor counts and a genuinely untracked write included: tests/test_gpu_derived_state.py.)"""
     rng = np.random.default_rng(41)
     ni, nq, f, k = 16_000, 64, 64, 10
     a = (rng.standard_normal((ni, f)) * 0.1).astype(np.float32)
