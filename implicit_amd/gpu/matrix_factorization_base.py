@@ -13,10 +13,11 @@ from ..recommender_base import RecommenderBase
 
 def _filter_items_from_sparse_matrix(items, query_items):
     """Re-index the liked-items matrix onto positions inside the sorted `items` subset, dropping
-    entries that are not in the subset (cpu/matrix_factorization_base.py:253-264)."""
+    entries that are not in the subset and, as the reference's eliminate_zeros() there does, stored zeros
+    (cpu/matrix_factorization_base.py:253-264)."""
     coo = query_items.tocoo()
     pos = np.clip(np.searchsorted(items, coo.col), 0, len(items) - 1)
-    keep = items[pos] == coo.col
+    keep = (items[pos] == coo.col) & (coo.data != 0)
     return csr_matrix((coo.data[keep], (coo.row[keep], pos[keep])), shape=(coo.shape[0], len(items)))
 
 

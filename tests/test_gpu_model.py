@@ -7,6 +7,8 @@ import pytest
 from numpy.testing import assert_array_equal
 from scipy.sparse import csr_matrix
 
+import serving_reference
+
 pytestmark = pytest.mark.gpu
 
 
@@ -55,6 +57,9 @@ def test_recommend_batch_matches_scalar(gpu):
     for u in range(50):
         i1, s1 = model.recommend(u, user_items[u], N=5, filter_already_liked_items=False)
         assert np.allclose(s1, scores[u]) and np.allclose(i1, ids[u])
+    # the trained checkerboard is full of near-ties, so the float64 restatement pins the scores, not the ids
+    want = serving_reference.recommend(model.user_factors.to_numpy(), model.item_factors.to_numpy(), userids, None, 5, False)
+    np.testing.assert_allclose(scores, want[1], rtol=1e-4, atol=1e-7)
     sel = np.array([2, 3, 4])
     ids, _ = model.recommend(sel, user_items[sel], N=1, filter_items=[0])
     assert all(0 not in row for row in ids)
@@ -86,8 +91,11 @@ def test_similar_items_and_users(gpu):
         assert scores[itemid][0] == pytest.approx(1.0, abs=1e-4)
         one_ids, one_scores = model.similar_items(itemid, N=10)
         assert all(i % 2 == itemid % 2 for i in one_ids)
+    want = serving_reference.similar(model.item_factors.to_numpy(), np.arange(50), 10)
+    np.testing.assert_allclose(model.similar_items(np.arange(50), N=10)[1], want[1], rtol=1e-4, atol=1e-7)
     ids, scores = model.similar_users(np.arange(4), N=5)
     assert ids.shape == (4, 5) and all(ids[u][0] == u for u in range(4))
+    np.testing.assert_allclose(scores, serving_reference.similar(model.user_factors.to_numpy(), np.arange(4), 5)[1], rtol=1e-4, atol=1e-7)
     sub = np.arange(0, 50, 2)
     ids, _ = model.similar_items(0, N=5, items=sub)
     assert set(ids) <= set(sub)
@@ -234,8 +242,10 @@ def test_partial_fit(gpu):
     assert model.user_factors.shape[0] == 106
     uf = model.user_factors.to_numpy()
     assert uf[105].any() and not uf[101].any()
-    ids, _ = model.recommend(105, new_user, N=3)
+    ids, scores = model.recommend(105, new_user, N=3)
     assert len(ids) == 3
+    want = serving_reference.recommend(uf, model.item_factors.to_numpy(), 105, new_user, 3)
+    np.testing.assert_allclose(scores, want[1], rtol=1e-4, atol=1e-7)
     new_item = csr_matrix(([1.0, 1.0], ([0, 0], [3, 7])), shape=(1, 106), dtype=np.float32)
     model.partial_fit_items([60], new_item)
     assert model.item_factors.shape[0] == 61 and model.item_factors.to_numpy()[60].any()
