@@ -156,6 +156,13 @@ class IVFModel(RecommenderBase):
         ids, scores = _first_unfiltered(ids, scores, drop, N)
         return (ids[0], scores[0]) if scalar else (ids, scores)
 
+    def explain(self, userid, user_items, itemid, user_weights=None, N=10):
+        """Exact: explanations do not search the index; forwarded to the wrapped model (ALS only)."""
+        return self.model.explain(userid, user_items, itemid, user_weights=user_weights, N=N)
+
+    def explain_batch(self, userids, user_items, itemids, N=10, user_weights=None):
+        return self.model.explain_batch(userids, user_items, itemids, N=N, user_weights=user_weights)
+
     def similar_users(self, userid, N=10, filter_users=None, users=None):
         raise NotImplementedError("similar_users isn't implemented with the approximate index "
                                   "(self.model.similar_users gives the exact result)")

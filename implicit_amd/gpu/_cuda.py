@@ -350,6 +350,34 @@ class LeastSquaresSolver:
             e.failed_row = failed.value  # -1 unless the factorisation itself failed (then: the smallest failing row)
             raise
 
+    def explain_factor(self, cui, YtY, Y, regularization, weights):
+        """NEW: the Cholesky factor L of every row's A_u = YtY + regularization I + sum (|c| - 1) y y^T (YtY UNregularised, the
+        matrix of least_squares_cholesky) into rows [u f, (u + 1) f) of `weights`, a float32 (cui.rows * f) x f Matrix: lower
+        triangular, zeros above the diagonal.  f <= 256, Y float32.  ValueError (with .failed_row) on a non-positive pivot."""
+        failed = ctypes.c_int64(-1)
+        try:
+            check(lib().imp_solver_explain_factor(self._h, cui._h, YtY._h, Y._h, float(regularization), weights._h,
+                                                  ctypes.byref(failed)))
+        except ValueError as e:
+            e.failed_row = failed.value
+            raise
+
+    def explain(self, cui, Y, weights, itemids, items_per_row, n):
+        """NEW: for row u of cui and each of its items_per_row ids in the IntVector `itemids` (row-major): the contributions
+        c_j (w . y_j), w = A_u^-1 y_i from the row's factor in `weights`, of the liked items (c_j > 0).  Returns host arrays
+        (total [pairs] float32, ids [pairs, n] int32, scores [pairs, n] float32): the n largest contributions under (score,
+        id) descending, padded with (-1, -FLT_MAX).  Bad ids, n < 1 or a mis-shaped `weights` raise ValueError."""
+        items_per_row, n = int(items_per_row), int(n)
+        if not (1 <= n < 2**31 and 1 <= items_per_row < 2**31):
+            raise ValueError("explain: n and items_per_row must be >= 1")
+        pairs = cui.shape[0] * items_per_row
+        total = np.empty(pairs, dtype=np.float32)
+        ids = np.empty((pairs, n), dtype=np.int32)
+        scores = np.empty((pairs, n), dtype=np.float32)
+        check(lib().imp_solver_explain(self._h, cui._h, Y._h, weights._h, itemids._h, items_per_row, n, _vp(total), _vp(ids),
+                                       _vp(scores)))
+        return total, ids, scores
+
     def calculate_loss(self, cui, X, Y, regularization):
         loss = ctypes.c_float(0)
         check(lib().imp_solver_calculate_loss(self._h, cui._h, X._h, Y._h, float(regularization),

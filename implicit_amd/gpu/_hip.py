@@ -77,6 +77,10 @@ _SIGNATURES = {
                                           ctypes.c_void_p, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)],
     "imp_solver_calculate_loss": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_float, c_f32_p],
+    "imp_solver_explain_factor": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                  ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)],
+    "imp_solver_explain": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     "imp_knn_create": [ctypes.c_size_t, c_void_pp],
     "imp_knn_destroy": [ctypes.c_void_p],
     "imp_knn_topk": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,

@@ -1,7 +1,8 @@
 """AlternatingLeastSquares on MI355X.
 
 Public surface of implicit/gpu/als.py:14-341 (fit / recalculate_user / recalculate_item /
-partial_fit_users / partial_fit_items / YtY / XtX / save / load / pickle, fit_callback) with the
+partial_fit_users / partial_fit_items / YtY / XtX / save / load / pickle, fit_callback), plus the CPU
+class's explain (cpu/als.py:351-416) and a batched explain_batch, with the
 numerics of the reference's *CPU* path, which is the parity oracle (implicit/cpu/als.py:98-202):
 
   * `alpha` scales the confidence matrix inside fit (cpu/als.py:133-134; the reference GPU fit
@@ -35,6 +36,7 @@ from .matrix_factorization_base import MatrixFactorizationBase
 log = logging.getLogger("implicit_amd")
 
 _CHOLESKY_MAX_FACTORS = 1024  # what the library's Cholesky takes (beyond 256: the triangle in a device workspace)
+_EXPLAIN_MAX_FACTORS = 256     # explain / explain_batch: the triangle stays in the LDS (csrc/explain.hip)
 
 
 class AlternatingLeastSquares(MatrixFactorizationBase):
@@ -230,6 +232,66 @@ class AlternatingLeastSquares(MatrixFactorizationBase):
         self.item_factors.assign_rows(itemids, new_rows)
         self._item_norms = self._item_norms_host = None
         self._YtY = self._YtY0 = None
+
+    # ---- explanations (implicit/cpu/als.py:351-416; the reference's GPU class has none) ---------------------------
+    def explain(self, userid, user_items, itemid, user_weights=None, N=10):
+        """Which liked items produced the score of `itemid` for `userid`, and how much each contributed.
+
+        `user_items` is the full users x items matrix, indexed by `userid` as in the reference.  Returns
+        (total_score, top_contributions, user_weights): the predicted score y_i . x_u (x_u as recalculate_user gives it),
+        the N largest contributions as a list of (itemid, score), best first under (score, itemid) descending, and the
+        user's weights.  UNLIKE the reference, whose user_weights is scipy's cho_factor tuple, this is a gpu.Matrix: the
+        lower-triangular Cholesky factor L (factors x factors, zeros above the diagonal) of
+        YtY + regularization I + sum (|c| - 1) y y^T.  Passing it back skips the factorisation and gives the same bits."""
+        user_items = check_csr(user_items)
+        total, ids, scores, user_weights = self.explain_batch([userid], user_items[userid], [itemid], N=N,
+                                                              user_weights=user_weights)
+        keep = ids[0, 0] >= 0
+        top = [(int(i), float(s)) for i, s in zip(ids[0, 0][keep], scores[0, 0][keep])]
+        return float(total[0, 0]), top, user_weights
+
+    def explain_batch(self, userids, user_items, itemids, N=10, user_weights=None):
+        """explain() for M items of each of B users in one call.  `user_items` has one row per entry of `userids`, as
+        recommend takes it; `itemids` is [B] or [B, M] (the ids recommend returns plug in).  Returns (total_scores [B, M]
+        float32, ids [B, M, N] int32, scores [B, M, N] float32, user_weights): lists shorter than N are padded with
+        (-1, -FLT_MAX); user_weights is a gpu.Matrix of B stacked factors, (B * factors) x factors, to pass back."""
+        user_items = check_csr(user_items)
+        userids = np.asarray(userids).reshape(-1)
+        count, f = len(userids), self.factors
+        if user_items.shape[0] != count:
+            raise ValueError("user_items must contain 1 row for every user in userids")
+        itemids = np.asarray(itemids)
+        if itemids.ndim == 1:
+            itemids = itemids[:, None]
+        if itemids.ndim != 2 or itemids.shape[0] != count or itemids.shape[1] < 1:
+            raise ValueError("itemids must be [len(userids)] or [len(userids), M] item ids")
+        items = self.item_factors.shape[0]
+        if itemids.size and (itemids.min() < 0 or itemids.max() >= items):
+            raise ValueError(f"item id out of range for explain: the model has {items} items")
+        if int(N) < 1:
+            raise ValueError("explain: N must be >= 1")
+        if f > _EXPLAIN_MAX_FACTORS:
+            raise ValueError(f"explain keeps a user's triangle on chip: factors must be <= {_EXPLAIN_MAX_FACTORS}, got {f}")
+        if self.alpha != 1.0:
+            user_items = self.alpha * user_items
+        C = gpu.CSRMatrix(user_items.astype(np.float32))
+        Y = _as_f32(self.item_factors)
+        if user_weights is None:
+            user_weights = gpu.Matrix.zeros(count * f, f)
+            try:
+                self.solver.explain_factor(C, self._YtY_unreg, Y, self.regularization, user_weights)
+            except ValueError as e:
+                row = getattr(e, "failed_row", -1)
+                if row < 0:
+                    raise
+                raise ValueError(f"the normal matrix of user {userids[row]} (row {row} of the batch) is not positive definite. "
+                                 "Try increasing the regularization parameter.") from e
+        elif not isinstance(user_weights, gpu.Matrix) or user_weights.shape != (count * f, f) or user_weights.itemsize != 4:
+            raise ValueError(f"user_weights must be the float32 gpu.Matrix of shape ({count * f}, {f}) an earlier call returned")
+        M = itemids.shape[1]
+        ids_dev = gpu.IntVector(np.ascontiguousarray(itemids, dtype=np.int32).reshape(-1))
+        total, ids, scores = self.solver.explain(C, Y, user_weights, ids_dev, M, int(N))
+        return total.reshape(count, M), ids.reshape(count, M, int(N)), scores.reshape(count, M, int(N)), user_weights
 
     # ---- cached gramians ------------------------------------------------------------------------------
     @property

@@ -193,6 +193,22 @@ int imp_solver_least_squares_cholesky(imp_solver *s, const imp_csr *cui, imp_mat
 /* calculate_loss(Cui, X, Y, regularization) (als.cu:253-281; oracle _als.pyx:257-308). */
 int imp_solver_calculate_loss(imp_solver *s, const imp_csr *cui, const imp_matrix *X,
                               const imp_matrix *Y, float regularization, float *loss_out);
+/* NEW: explanations of ALS recommendations (the reference explains on the CPU only, implicit/cpu/als.py explain).  For every
+ * row u of cui (alpha already applied) explain_factor builds A_u = YtY + regularization I + sum_j (|c_j| - 1) y_j y_j^T --
+ * YtY is UNregularised, the matrix of the Cholesky half sweep -- and writes its Cholesky factor L, lower triangular with zeros
+ * above the diagonal, into rows [u f, (u + 1) f) of `weights`: caller-allocated fp32, (cui.rows * f) x f.  f <= 256; Y fp32.
+ * On a non-positive pivot returns IMP_INVALID_ARGUMENT and *failed_row = the smallest failing row (else -1), as
+ * imp_solver_least_squares_cholesky. */
+int imp_solver_explain_factor(imp_solver *s, const imp_csr *cui, const imp_matrix *YtY, const imp_matrix *Y,
+                              double regularization, imp_matrix *weights, int64_t *failed_row);
+/* NEW: for row u and each of its items_per_row ids i = itemids[u * items_per_row + m]: w = A_u^-1 y_i by two triangular solves
+ * with the row's L from `weights`; liked item j (c_j > 0) contributes s_j = c_j (w . y_j).  Outputs are HOST buffers:
+ * total[rows * items_per_row] = sum_j s_j, and ids / scores[rows * items_per_row * n], the n largest contributions under
+ * (score descending, id descending), padded with (-1, -FLT_MAX).  Deterministic: no floating-point atomics.  Ids outside Y,
+ * n < 1, items_per_row < 1 and a weights matrix that is not fp32 (cui.rows * f) x f are IMP_INVALID_ARGUMENT before any
+ * launch. */
+int imp_solver_explain(imp_solver *s, const imp_csr *cui, const imp_matrix *Y, const imp_matrix *weights,
+                       const imp_intvector *itemids, int items_per_row, int n, float *total, int32_t *ids, float *scores);
 
 /* ---- KnnQuery (knn.h:15-35, knn.cu:56-265) ---------------------------------------------------- */
 /* KnnQuery(max_temp_memory): 0 = min(free/2, 4 GiB) (knn.cu:56-75). */
