@@ -161,6 +161,7 @@ __global__ __launch_bounds__(256) void explain_factor_kernel(const int32_t *__re
 // ---- contribution kernel --------------------------------------------------------------------------------------------------------
 // Sortable key of a contribution: the score's bits mapped so that unsigned order = float order, then the item id + 1 (so that no
 // valid key is 0, the mark of an entry that contributes nothing).  Unsigned key order = (score, id) order.
+// (Not select_ops.h's key: this one stores id + 1, keeps -0.0 distinct from +0.0 and breaks ties by position; golden files pin it.)
 __device__ __forceinline__ key_t64 make_key(float score, int id) {
   unsigned u = __builtin_bit_cast(unsigned, score);
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);

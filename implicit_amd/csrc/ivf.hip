@@ -35,6 +35,7 @@
 #include <functional>
 
 #include "common.h"
+#include "select_ops.h"  // the score/id key (make_key, key_id, key_score), block_sort_desc
 
 struct imp_ivf {
   size_t n = 0, f = 0;
@@ -66,13 +67,6 @@ constexpr int kIvfMaxK = 1024;
 constexpr int kIvfRun = 1024;             // elements per run of the grouping, at least
 constexpr int64_t kIvfMaxCounters = (int64_t)1 << 24;  // runs x keys of the grouping's counter table, at most
 
-__device__ __forceinline__ uint32_t ivf_ordered(float s) {
-  uint32_t u = __float_as_uint(s);
-  if (u == 0x80000000u) u = 0u;  // -0.0 ties with +0.0
-  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float ivf_unordered(uint32_t u) { return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-__device__ __forceinline__ uint64_t ivf_key(float s, int id) { return ((uint64_t)ivf_ordered(s) << 32) | (uint32_t)id; }
 __device__ __forceinline__ uint64_t ivf_max64(uint64_t a, uint64_t b) { return a < b ? b : a; }
 __device__ __forceinline__ int64_t ivf_min64(int64_t a, int64_t b) { return a < b ? a : b; }
 
@@ -353,12 +347,12 @@ __global__ __launch_bounds__(256) void ivf_argmax_kernel(const float *__restrict
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   uint64_t best = 0;
-  for (int c = lane; c < ncol; c += 64) best = ivf_max64(best, ivf_key(S[row * ncol + c], c));
+  for (int c = lane; c < ncol; c += 64) best = ivf_max64(best, make_key(S[row * ncol + c], c));
   for (int m = 32; m > 0; m >>= 1) {
     const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), m), lo = __shfl_xor((uint32_t)best, m);
     best = ivf_max64(best, ((uint64_t)hi << 32) | lo);
   }
-  if (lane == 0) out[row] = (int32_t)(uint32_t)best;
+  if (lane == 0) out[row] = key_id(best);
 }
 
 // Candidates of query q.  Dense (probes == nullptr): S[q * ncand .. + ncand), id = column.  Grouped: for each of its P probes
@@ -376,7 +370,7 @@ struct IvfSelectArgs {
 template <typename F> __device__ __forceinline__ void ivf_for_each_candidate(const IvfSelectArgs &a, int64_t q, F &&body) {
   if (!a.probes) {
     const float *s = a.S + q * a.ncand;
-    for (int v = threadIdx.x; v < a.ncand; v += 256) body(ivf_key(s[v], v));
+    for (int v = threadIdx.x; v < a.ncand; v += 256) body(make_key(s[v], v));
     return;
   }
   for (int j = 0; j < a.P; ++j) {
@@ -384,7 +378,7 @@ template <typename F> __device__ __forceinline__ void ivf_for_each_candidate(con
     const int lb = a.list_off[l], len = a.list_off[l + 1] - lb;
     const float *s = a.S + a.score_base[l] + (int64_t)(p - a.pair_off[l]) * len;
     const int32_t *ids = a.list_ids + lb;
-    for (int v = threadIdx.x; v < len; v += 256) body(ivf_key(s[v], ids[v]));
+    for (int v = threadIdx.x; v < len; v += 256) body(make_key(s[v], ids[v]));
   }
 }
 
@@ -501,23 +495,13 @@ __global__ __launch_bounds__(256) void ivf_select_kernel(const IvfSelectArgs a) 
     }
   });
   __syncthreads();
-  for (int i = (int)want + tid; i < a.kpad; i += 256) cand[i] = 0;
-  for (int size = 2; size <= a.kpad; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int i = tid; i < a.kpad; i += 256) {
-        const int partner = i ^ stride;
-        if (partner > i) {
-          const uint64_t x = cand[i], y = cand[partner];
-          if ((x < y) == ((i & size) == 0)) cand[i] = y, cand[partner] = x;
-        }
-      }
-    }
+  for (int i = (int)want + tid; i < a.kpad; i += 256) cand[i] = 0;  // pads sort last
   __syncthreads();
+  block_sort_desc<256>(cand, a.kpad);
   for (int i = tid; i < a.k; i += 256) {
     const bool filled = i < (int)want;
-    a.out_ids[q * a.k + i] = filled ? (int32_t)(uint32_t)cand[i] : -1;
-    a.out_dist[q * a.k + i] = filled ? ivf_unordered((uint32_t)(cand[i] >> 32)) : -FLT_MAX;
+    a.out_ids[q * a.k + i] = filled ? key_id(cand[i]) : -1;
+    a.out_dist[q * a.k + i] = filled ? key_score(cand[i]) : -FLT_MAX;
   }
 }
 

@@ -25,6 +25,7 @@
 // in registers, lane l holding positions l, l+64, ...; each candidate that beats the list's last kept entry is inserted
 // with one ballot per register and a shift by shuffles.  k above 64*R runs further rounds, each over the candidates strictly
 // below the last entry written, until k entries are written or the candidates run out -- exact for any k (R = 4 there).
+// (Not on select_ops.h: its keys carry fp32 scores, these scores are double and never leave registers; golden files pin the order.)
 #include <cfloat>
 #include <cstring>
 #include <vector>

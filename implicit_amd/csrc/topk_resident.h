@@ -1,4 +1,4 @@
-// Scoring GEMM of the top-k path with the QUERY operand resident in registers (round 6).  Included by topk.hip (namespace imp).
+// Scoring GEMM of the top-k path with the QUERY operand resident in registers (round 6).  Included by topk.hip.
 //
 // Replaces the 128 x 128 block-tile form of score_gemm_direct_kernel for the two-term fp16 product (l h, h l, h h on
 // v_mfma_f32_32x32x16_f16; reference semantics: the fp32 GEMM of implicit/gpu/knn.cu:131-147 == implicit/cpu/topk.pyx:45-47).
@@ -19,7 +19,18 @@
 // the EXACT item maximum (the cached split pass sees every value: no sampled maximum, no overflow case left).
 #ifndef IMPLICIT_AMD_CSRC_TOPK_RESIDENT_H_
 #define IMPLICIT_AMD_CSRC_TOPK_RESIDENT_H_
+#include <algorithm>
+#include <cfloat>
+#include <stdexcept>
+#include <type_traits>
 
+#include "common.h"       // ctx(), stream(), IMP_CHECK_HIP
+#include "select_ops.h"   // the candidates' keys
+#include "topk_select.h"  // EmitArgs, kTileItems
+
+namespace imp {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // accumulator of a 32 x 32 MFMA tile (also topk.hip's)
 typedef _Float16 rq_f16x8 __attribute__((ext_vector_type(8)));
 template <int N, int I = 0, typename Fn> __device__ __forceinline__ void rq_static_for(Fn &&fn) {
   if constexpr (I < N) {
@@ -426,7 +437,7 @@ __global__ __launch_bounds__(256, 2) void score_resident_kernel(ResidentArgs a) 
       const unsigned n_st = min(st_n, (unsigned)kRqStageCap);
       for (unsigned i = threadIdx.x; i < n_st; i += 256) {
         const unsigned long long key = st_key[i];
-        rq_append(a.emit, qb * QROWS + (int)st_row[i], (int)(uint32_t)key, key);
+        rq_append(a.emit, qb * QROWS + (int)st_row[i], key_id(key), key);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the appends' memory operations share the counter of the counted DMA waits)
       __syncthreads();
@@ -566,7 +577,7 @@ __global__ __launch_bounds__(256, 2) void score_resident_kernel(ResidentArgs a) 
     const unsigned n_all = st_n, n_st = min(n_all, (unsigned)kRqStageCap);
     for (unsigned i = threadIdx.x; i < n_st; i += 256) {
       const unsigned long long key = st_key[i];
-      rq_append(a.emit, qb * QROWS + (int)st_row[i], (int)(uint32_t)key, key);
+      rq_append(a.emit, qb * QROWS + (int)st_row[i], key_id(key), key);
     }
     if (n_all > (unsigned)kRqStageCap || st_over) {
       // the staging buffer overflowed (a workgroup expects ~640 of its 1536 entries): candidates were dropped, WHOSE is not known --
@@ -736,4 +747,5 @@ template <int MODE> static void launch_score_resident(int KS, ResidentArgs a, in
 static inline size_t rq_query_pad(size_t rows) { return (rows + 255) / 256 * 256; }
 static inline int rq_ks_for(int f) { return f <= 32 ? 2 : (f <= 64 ? 4 : (f <= 128 ? 8 : (f <= 256 ? 16 : 0))); }
 
+}  // namespace imp
 #endif  // IMPLICIT_AMD_CSRC_TOPK_RESIDENT_H_

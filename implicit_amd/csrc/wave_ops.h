@@ -9,9 +9,9 @@
 namespace imp {
 
 // ---- wave64 reductions on DPP (no LDS crossbar) --------------------------------------------------
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
+template <int CTRL, int ROW_MASK = 0xF, typename T>
+__device__ __forceinline__ T dpp_mov(T v) {  // T: float, int32_t or uint32_t
+  return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
 }
 
 // Sum over the 64 lanes, returned in every lane (via SGPR broadcast of lane 63).
@@ -25,17 +25,27 @@ __device__ __forceinline__ float wave_allsum(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// op over the 64 lanes, in every lane, for an op that is associative, commutative and idempotent (a maximum): a row_ror tree
+// inside each 16-lane row, then the four rows' results through SGPRs.
+template <typename T, typename Op> __device__ __forceinline__ T wave_allreduce_idem(T v, Op op) {
+  v = op(v, dpp_mov<0x128>(v));  // row_ror:8
+  v = op(v, dpp_mov<0x124>(v));
+  v = op(v, dpp_mov<0x122>(v));
+  v = op(v, dpp_mov<0x121>(v));  // every lane: the result of its 16-lane row
+  const T r0 = __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
+  const T r1 = __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
+  const T r2 = __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
+  const T r3 = __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
+  return op(op(r0, r1), op(r2, r3));
+}
+
 // Maximum over the 64 lanes, in every lane (NaN inputs are dropped by fmaxf).
 __device__ __forceinline__ float wave_allmax(float v) {
-  v = fmaxf(v, dpp_mov<0x128>(v));
-  v = fmaxf(v, dpp_mov<0x124>(v));
-  v = fmaxf(v, dpp_mov<0x122>(v));
-  v = fmaxf(v, dpp_mov<0x121>(v));  // every lane: the maximum of its 16-lane row
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-  return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+  return wave_allreduce_idem(v, [](float a, float b) { return fmaxf(a, b); });
+}
+// the same for unsigned keys (ordered scores: select_ops.h)
+__device__ __forceinline__ uint32_t wave_allmax_u32(uint32_t v) {
+  return wave_allreduce_idem(v, [](uint32_t a, uint32_t b) { return max(a, b); });
 }
 
 // Sum over an aligned group of G = 16, 32 or 64 lanes, in every lane of the group.  An xor butterfly: both lanes of a pair

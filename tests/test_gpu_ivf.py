@@ -164,6 +164,28 @@ def test_zero_rows(gpu):
     _check_search(vectors, vectors[:64], got_ids, got_scores, want_ids, want_scores)
 
 
+def test_select_when_the_far_tail_does_not_fit_in_lds(gpu):
+    """ivf_select_kernel with its radix select on the score segments themselves: every score is an integer in [1024, 1280),
+    so all 3 000 keys share sign, exponent and the two top mantissa bits -- one bucket of the 11-bit histogram, more than the
+    2 048 keys the LDS copy holds (a condition on the scores alone; nothing at run time reports it).  Scores are exact in fp32
+    and full of ties: ids and scores equal the float64 brute force under (score desc, id desc), no near-tie exceptions."""
+    rng = np.random.default_rng(17)
+    n, f = 3000, 8
+    vectors = rng.integers(-20, 21, size=(n, f)).astype(np.float32)
+    vectors[:, 0] = rng.integers(1100, 1200, size=n)
+    queries = np.zeros((3, f), dtype=np.float32)
+    queries[:, 0] = 1
+    queries[0, 1], queries[1, 2], queries[2, 3] = 1, -1, 2   # scores v0 + v1, v0 - v2, v0 + 2 v3: within [1060, 1240)
+    scores = vectors.astype(np.float64) @ queries.astype(np.float64).T
+    assert (scores == np.round(scores)).all() and scores.min() >= 1024 and scores.max() < 1280
+    ix = gpu.IVFIndex.build(vectors, 4, 4, init_rows=np.array([0, 1, 2, 3]))
+    got_ids, got_scores = ix.search(queries, 10, 4)
+    want_ids, want_scores = ref.brute_force(vectors, queries, 10)
+    np.testing.assert_array_equal(got_ids, want_ids)
+    np.testing.assert_array_equal(got_scores, want_scores.astype(np.float32))
+    assert any(len(set(row)) < len(row) for row in want_scores)  # (ties among the winners)
+
+
 @pytest.fixture(scope="module")
 def lopsided(gpu):
     """6000 vectors in 6 planted clusters: one of 3500, one of a single vector."""

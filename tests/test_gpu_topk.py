@@ -137,6 +137,36 @@ def test_pruned_select_resolves_ties_at_the_kth_score(gpu, oracle, k):
     assert_array_equal(d, want_d)
 
 
+def test_exact_select_with_its_candidates_in_global_scratch(gpu, oracle):
+    """k > 8 192: the k winners of select_kernel (padded to 16 384 keys = 128 KiB) no longer fit its 96 KiB of LDS, so the
+    gather and the sort run on global scratch (use_lds == 0); such a k is also beyond every candidate capacity, i.e. the call
+    is on the general path.  Small-integer factors: fp32 scores are exact and full of ties, the k-th score included (the radix
+    walk ends ambiguous and the tie rule decides), so ids AND scores must equal the oracle's heap bit for bit.
+    Route seen in the A/B run of profiles/select_ops.txt: scopes score_gemm_lds + topk_select."""
+    rng = np.random.default_rng(41)
+    items = rng.integers(-3, 4, size=(9000, 8)).astype(np.float32)
+    queries = rng.integers(-3, 4, size=(3, 8)).astype(np.float32)
+    k = 8200
+    want_ids, want_d = oracle.topk(items, queries, k)
+    scores = queries @ items.T  # (exact: small integers)
+    assert all((scores[r] == want_d[r, -1]).sum() > (want_d[r] == want_d[r, -1]).sum() for r in range(3))  # k cuts a tie group
+    ids, d = gpu.KnnQuery().topk(gpu.Matrix(items), gpu.Matrix(queries), k)
+    assert_array_equal(ids, want_ids)
+    assert_array_equal(d, want_d)
+
+
+def test_pruned_select_beyond_the_tile_list(gpu):
+    """More tiles of 64 items than the pruned select can list in LDS (n_tiles = 4 097 > kCandCap = 4 096): the threshold comes
+    from the radix walk over the tile maxima and the hit tiles are scanned wavefront by wavefront as they are found; k = 300 keeps
+    the call on the materialising path and the candidates on the bitonic sort.  Judged by the float64 rule of
+    test_gpu_topk_fuzz.py.  (The listed form with the radix walk, 1 024 < n_tiles <= 4 096 and k = 300, is reached by two draws
+    of test_random_shapes_against_float64[13].)  Branch seen in the IMP_TOPK_DEBUG run of profiles/select_ops.txt: scopes
+    score_gemm + topk_select_pruned, no row handed to the exact select."""
+    from test_gpu_topk_fuzz import _check
+
+    _check(gpu, gpu.KnnQuery(), np.random.default_rng(43), 262_208, 16, 2, 300, "normal", np.float32, False, False, False)
+
+
 def test_topk_zero_queries_and_all_filtered_tail(gpu, oracle):
     """Users without interactions (zero factors) and N larger than the unfiltered items
     (recommender_base_test.py:54-57): ids identical to the CPU path, filtered entries score -FLT_MAX."""
