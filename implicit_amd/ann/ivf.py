@@ -163,6 +163,15 @@ class IVFModel(RecommenderBase):
     def explain_batch(self, userids, user_items, itemids, N=10, user_weights=None):
         return self.model.explain_batch(userids, user_items, itemids, N=N, user_weights=user_weights)
 
+    def rank_items(self, userid, user_items, selected_items, N=None, filter_already_liked_items=False,
+                   recalculate_user=False):
+        """Exact: ranking given candidates does not search the index; forwarded to the wrapped model."""
+        return self.model.rank_items(userid, user_items, selected_items, N=N,
+                                     filter_already_liked_items=filter_already_liked_items, recalculate_user=recalculate_user)
+
+    def score_items(self, userid, selected_items, user_items=None, recalculate_user=False):
+        return self.model.score_items(userid, selected_items, user_items=user_items, recalculate_user=recalculate_user)
+
     def similar_users(self, userid, N=10, filter_users=None, users=None):
         raise NotImplementedError("similar_users isn't implemented with the approximate index "
                                   "(self.model.similar_users gives the exact result)")

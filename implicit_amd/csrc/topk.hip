@@ -716,6 +716,10 @@ struct imp_knn {
   }
 };
 
+namespace imp {
+size_t knn_temp_budget(const imp_knn *k) { return k->max_temp_memory; }  // for rank.hip, which shares the handle's budget only
+}
+
 // ---- host side of imp_knn_topk: checks -> operands -> outputs -> (emit | materialise) -> deliver ----------------------------
 // The A/B and parity switches of the top-k entry point, read from the environment once per process.  Every route they select
 // stays reachable: tests/test_gpu_topk_routes.py runs each of them.

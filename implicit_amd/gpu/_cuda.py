@@ -83,6 +83,31 @@ class KnnQuery:
             item_filter._h if item_filter is not None else None))
         return ids, dist
 
+    def rank(self, items, query, offsets, candidates, n=0, liked=None):
+        """NEW: scores the candidate list of every query row -- row r against items[candidates[offsets[r]:offsets[r + 1]]] --
+        and, for n >= 1, ranks it (csrc/rank.hip).  offsets / candidates: host arrays (int64 / int32).  liked: a scipy CSR
+        pattern with one row per query and sorted indices, or None; a candidate stored in its row scores -FLT_MAX.  n == 0:
+        returns the scores, aligned with `candidates`; n >= 1: (ids, scores), rows x n, best first, padded with (-1, -FLT_MAX)."""
+        if not isinstance(items, Matrix) or not isinstance(query, Matrix):
+            raise TypeError("KnnQuery.rank expects implicit.gpu.Matrix arguments")
+        n, rows = int(n), query.shape[0]
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        candidates = np.ascontiguousarray(candidates, dtype=np.int32)
+        if offsets.shape != (rows + 1,) or candidates.ndim != 1 or len(candidates) != (offsets[-1] if rows else 0):
+            raise ValueError("rank: offsets must hold one entry per query row plus one and end at len(candidates)")
+        indptr = indices = None
+        if liked is not None:
+            if liked.shape[0] != rows:
+                raise ValueError("rank: liked must contain 1 row for every query row")
+            indptr = np.ascontiguousarray(liked.indptr, dtype=np.int64)
+            indices = np.ascontiguousarray(liked.indices, dtype=np.int32)
+        ids = np.zeros((rows, n), dtype=np.int32) if n > 0 else None
+        scores = np.zeros((rows, n) if n > 0 else len(candidates), dtype=np.float32)
+        check(lib().imp_knn_rank(self._h, items._h, query._h, _vp(offsets), _vp(candidates), n,
+                                 _vp(indptr) if liked is not None else None, _vp(indices) if liked is not None else None,
+                                 _vp(ids) if n > 0 else None, _vp(scores)))
+        return (ids, scores) if n > 0 else scores
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().imp_knn_destroy(self._h)

@@ -85,6 +85,8 @@ _SIGNATURES = {
     "imp_knn_destroy": [ctypes.c_void_p],
     "imp_knn_topk": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    "imp_knn_rank": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     "imp_random_create": [ctypes.c_int64, c_void_pp],
     "imp_random_destroy": [ctypes.c_void_p],
     "imp_random_uniform": [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_float, ctypes.c_float,

@@ -9,6 +9,7 @@ from scipy.sparse import csr_matrix
 import implicit_amd.gpu as gpu
 
 from ..recommender_base import RecommenderBase
+from ..utils import candidate_form, candidate_lists
 
 
 def _filter_items_from_sparse_matrix(items, query_items):
@@ -84,6 +85,56 @@ class MatrixFactorizationBase(RecommenderBase):
     def _liked_filter(liked):
         """The already-liked filter of a top-k query: the (row, col) pattern of the CSR matrix `liked`, None when empty."""
         return gpu.COOMatrix.from_csr_pattern(liked) if liked.nnz else None  # the filter reads (row, col) only
+
+    # ---- per-user candidate lists: the second stage of retrieve-then-rank (KnnQuery.rank) ----------------
+    def _rank(self, userid, user_items, selected_items, n, filter_liked, recalculate_user):
+        """The shared front of rank_items / score_items: (offsets, what KnnQuery.rank returns for n)."""
+        scalar = np.isscalar(userid)
+        batch = 1 if scalar else len(userid)
+        if filter_liked or recalculate_user:
+            if not isinstance(user_items, csr_matrix):
+                raise ValueError("user_items needs to be a CSR sparse matrix")
+            if user_items.shape[0] != batch:
+                raise ValueError("user_items must contain 1 row for every user in userids")
+        offsets, candidates = candidate_lists(selected_items, batch)
+        if len(candidates) and (candidates.max() >= self.item_factors.shape[0] or candidates.min() < 0):
+            raise IndexError("Some itemids are not in the model")
+        query = self.recalculate_user(userid, user_items) if recalculate_user else self._user_query(userid)
+        liked = None
+        if filter_liked and user_items.nnz:
+            liked = user_items if user_items.has_sorted_indices else user_items.sorted_indices()
+        if n is None:
+            n = int(np.diff(offsets).max()) if batch else 0
+            if n == 0:  # nothing to rank in any list
+                return offsets, (np.zeros((batch, 0), dtype=np.int32), np.zeros((batch, 0), dtype=np.float32))
+        return offsets, self.knn.rank(self.item_factors, query, offsets, candidates, n, liked)
+
+    def rank_items(self, userid, user_items, selected_items, N=None, filter_already_liked_items=False,
+                   recalculate_user=False):
+        """NEW (stock implicit had rank_items and dropped it): orders every user's own candidate list.  selected_items: 1-d ids
+        (one list shared by every user), a 2-d [B, M] integer ndarray (entries < 0 are padding) or a sequence of B 1-d
+        arrays.  Returns (ids, scores), [N] for a scalar userid and [B, N] otherwise, best first under (score desc, id desc);
+        N=None: the longest list; a list shorter than N is padded with (-1, -FLT_MAX).  A liked candidate scores -FLT_MAX
+        and stays in the list (filter_already_liked_items).  user_items is read only when filtering or recalculating."""
+        if N is not None and int(N) < 1:
+            raise ValueError("N must be >= 1 (or None for the longest list)")
+        _, (ids, scores) = self._rank(userid, user_items, selected_items, None if N is None else int(N),
+                                      filter_already_liked_items, recalculate_user)
+        return (ids[0], scores[0]) if np.isscalar(userid) else (ids, scores)
+
+    def score_items(self, userid, selected_items, user_items=None, recalculate_user=False):
+        """NEW: the scores of (user, item) pairs, aligned with selected_items (forms as in rank_items): [M] / [B, M] for a
+        shared list, [B, M] with -FLT_MAX at the padding for a 2-d array, a list of B arrays for ragged lists.  The same
+        kernel as rank_items: a pair's score has the same bits in both."""
+        form = candidate_form(selected_items)
+        offsets, scores = self._rank(userid, user_items, selected_items, 0, False, recalculate_user)
+        if form == "ragged":
+            return [scores[offsets[r]:offsets[r + 1]] for r in range(len(offsets) - 1)]
+        if form == "padded":
+            out = np.full(selected_items.shape, -np.finfo(np.float32).max, dtype=np.float32)
+            out[selected_items >= 0] = scores
+            return out
+        return scores if np.isscalar(userid) else scores.reshape(len(offsets) - 1, len(selected_items))
 
     # ---- cosine similarity -------------------------------------------------------------------------
     def _similar(self, factors, norms_dev, norms_host, queryid, N, subset, filter_ids, what, query_factors=None):

@@ -34,6 +34,8 @@ import time
 
 import numpy as np
 
+from ..utils import candidate_form, candidate_lists
+
 
 def shard_offsets(n_rows, nranks, weights=None):
     """Contiguous row ranges, one per rank.  With `weights` (e.g. nnz per row) the cut points balance
@@ -430,6 +432,26 @@ def recommend(model, comm, userids, user_items, N=10, **kwargs):
         return lo, hi, np.zeros((0, N), dtype=np.int32), np.zeros((0, N), dtype=np.float32)
     rows = user_items[lo:hi] if user_items is not None else None
     ids, scores = model.recommend(userids[lo:hi], rows, N=N, **kwargs)
+    return lo, hi, ids, scores
+
+
+def rank_items(model, comm, userids, user_items, selected_items, N=None, **kwargs):
+    """This rank's slice of model.rank_items(userids, user_items, selected_items, N, ...): (lo, hi, ids, scores).  N=None is
+    the longest list of the WHOLE batch, so that the slices of all ranks stack into the one-call result."""
+    userids = np.asarray(userids)
+    if userids.ndim != 1:
+        raise ValueError("the sharded rank_items takes a batch (1-d array) of user ids")
+    if user_items is not None and user_items.shape[0] != len(userids):
+        raise ValueError("user_items must contain 1 row for every user in userids")
+    offsets, _ = candidate_lists(selected_items, len(userids))
+    if N is None:
+        N = int(np.diff(offsets).max()) if len(userids) else 0
+    lo, hi = query_slice(len(userids), comm)
+    if hi == lo or N == 0:
+        return lo, hi, np.zeros((hi - lo, N), dtype=np.int32), np.zeros((hi - lo, N), dtype=np.float32)
+    rows = user_items[lo:hi] if user_items is not None else None
+    mine = selected_items if candidate_form(selected_items) == "shared" else selected_items[lo:hi]
+    ids, scores = model.rank_items(userids[lo:hi], rows, mine, N=N, **kwargs)
     return lo, hi, ids, scores
 
 

@@ -39,6 +39,59 @@ def nonzeros(m, row):
         yield m.indices[k], m.data[k]
 
 
+def _id_array(a, what):
+    a = np.asarray(a)
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must hold integer item ids, got dtype {a.dtype}")
+    return a if a.dtype.kind in "iu" else a.astype(np.int32)  # (an empty float array: what np.asarray makes of [])
+
+
+def candidate_form(selected_items):
+    """How rank_items / score_items read `selected_items`: "shared" (1-d ids: one list for every user), "padded" (a 2-d
+    ndarray, one row per user, entries < 0 are padding) or "ragged" (a sequence of 1-d arrays, one per user)."""
+    if isinstance(selected_items, np.ndarray) and selected_items.dtype != object:
+        if selected_items.ndim == 1:
+            return "shared"
+        if selected_items.ndim == 2:
+            return "padded"
+        raise ValueError(f"selected_items must be 1- or 2-dimensional, got {selected_items.ndim} dimensions")
+    if np.isscalar(selected_items) or not hasattr(selected_items, "__len__"):
+        raise ValueError("selected_items must be an array of item ids or a sequence of such arrays")
+    if all(np.isscalar(x) for x in selected_items):
+        return "shared"
+    return "ragged"
+
+
+def candidate_lists(selected_items, batch):
+    """The candidate lists of `batch` users as CSR: (offsets [batch + 1] int64, candidates int32), user r owning
+    candidates[offsets[r]:offsets[r + 1]] in the order given.  Pure host code."""
+    form = candidate_form(selected_items)
+    if form == "shared":
+        ids = _id_array(selected_items, "selected_items")
+        lengths = np.full(batch, len(ids), dtype=np.int64)
+        flat = np.tile(ids, batch)
+    elif form == "padded":
+        ids = _id_array(selected_items, "selected_items")
+        if ids.shape[0] != batch:
+            raise ValueError("selected_items must contain 1 row for every user in userids")
+        keep = ids >= 0
+        lengths = keep.sum(axis=1).astype(np.int64)
+        flat = ids.reshape(-1) if keep.all() else ids[keep]  # row-major: every row's entries in their own order
+    else:
+        if len(selected_items) != batch:
+            raise ValueError("selected_items must contain 1 list for every user in userids")
+        rows = [_id_array(x, "every list of selected_items") for x in selected_items]
+        if any(x.ndim != 1 for x in rows):
+            raise ValueError("every list of selected_items must be 1-dimensional")
+        lengths = np.array([len(x) for x in rows], dtype=np.int64)
+        flat = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int32)
+    if flat.size and flat.dtype != np.int32 and (flat.max() > np.iinfo(np.int32).max or flat.min() < np.iinfo(np.int32).min):
+        raise IndexError("Some itemids are not in the model")
+    offsets = np.zeros(batch + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    return offsets, np.ascontiguousarray(flat, dtype=np.int32)
+
+
 def random_factors(rng, rows, cols, scale=0.01, workers=None):
     """`rng.random((rows, cols), dtype=float32) * scale` -- the CPU path's initial factors (implicit/cpu/als.py:144-147) --
     with the SAME bits and the same generator state afterwards, drawn by a pool of threads: PCG64 can jump ahead, one 64-bit

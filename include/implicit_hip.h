@@ -222,6 +222,23 @@ int imp_knn_destroy(imp_knn *k);
 int imp_knn_topk(imp_knn *k, const imp_matrix *items, const imp_matrix *query, int topk,
                  int32_t *indices, float *distances, const imp_matrix *item_norms,
                  const imp_coo *query_filter, const imp_intvector *item_filter);
+/* NEW: scores, and for n >= 1 ranks, a candidate list per query row (csrc/rank.hip).  items (n_items x w) and query (rows x w): fp32
+ * or fp16 in any pairing, any w >= 1.  HOST inputs: offsets[rows + 1] and candidates[offsets[rows]], row r being scored against
+ * the items candidates[offsets[r] .. offsets[r + 1]); optionally the liked pattern as CSR, one row per query, columns strictly
+ * increasing inside a row (both pointers NULL: no filter).  A score is the dot product over the w stored columns, fp16 widened
+ * exactly, products and sums fp32 in an order that depends on w alone: the same (query row, item row) bits give the same
+ * score bits whatever the list, row, chunk or mode.  A candidate stored in the query's liked row scores -FLT_MAX and takes part
+ * like any other.  HOST outputs: n == 0: scores[offsets[rows]] in the candidates' own order, `indices` is not touched; n >= 1:
+ * indices / scores[rows x n], each row the best min(n, length) candidates of its list, best first in the total order (score
+ * desc, id desc, -0.0 as +0.0), the tail id -1, score -FLT_MAX; an id repeated in a list is scored and returned as often.  Rows
+ * are processed in chunks that fit the handle's max_temp_memory; the chunking changes no result.  Deterministic: no
+ * floating-point atomics.  IMP_INVALID_ARGUMENT before any launch, nothing written: column counts that differ, a matrix neither
+ * fp32 nor fp16, offsets that do not start at 0 or that decrease, a candidate id outside [0, n_items), a liked row not strictly
+ * increasing, n < 0, a list of more than 4096 candidates with n > 1024, a single row whose temporaries exceed max_temp_memory
+ * (the message names the bytes). */
+int imp_knn_rank(imp_knn *k, const imp_matrix *items, const imp_matrix *query, const int64_t *offsets,
+                 const int32_t *candidates, int n, const int64_t *liked_indptr, const int32_t *liked_indices,
+                 int32_t *indices, float *scores);
 
 /* ---- RandomState (random.h:10-21, random.cu:14-40) ------------------------------------------- */
 int imp_random_create(int64_t seed, imp_random **out);
