@@ -32,6 +32,10 @@ void launch_team_tile64(const imp_csr *C, int f, int width, int first, int count
 template <typename T>
 void launch_team_chain(const imp_csr *C, int f, const int (&first)[3], const int (&count)[3], T *X, const T *Y, const float *A0, int cg_steps,
                        const char *name);
+// als_cg_qf.hip: (256,512] and the short rows -- the two 1024-thread classes -- in one persistent launch (fp32 storage, f = 128)
+template <typename T>
+void launch_wide_chain(const imp_csr *C, int f, const int (&first)[2], const int (&count)[2], T *X, const T *Y, const float *A0, int cg_steps,
+                       const char *name);
 
 template <int F, typename T> static void run_classes_q(const imp_csr *C, T *X, const T *Y, const float *A0, int cg_steps) {
   const int32_t *b = C->bin_start;  // classes: 1 (256,512]  2 (128,256]  3 (64,128]  4 (32,64]  5 (16,32]  6 (0,16]
@@ -41,18 +45,20 @@ template <int F, typename T> static void run_classes_q(const imp_csr *C, T *X, c
     if constexpr (kHalf) launch_team_tile64<T>(C, F, width32 / 2, lo, hi - lo, X, Y, A0, cg_steps, name);
     else launch_team_fused<T>(C, F, width32, lo, hi - lo, X, Y, A0, cg_steps, name);
   };
-  team(16, b[1], b[2], "als_cg_team16_rows");  // (names: the row class)
-  // (128,256], (64,128], (32,64]: fp32 storage at f = 128 chains them in one launch.  A profiled run with no name filter -- a
-  // per-kernel pass, which wants a scope per class -- keeps the three launches, as do float16 storage (packed tiles) and f = 64
-  // (launch_team_chain has the reason).
+  // fp32 storage at f = 128 chains (128,256], (64,128], (32,64] in one launch and (256,512] with the short rows in another.  A
+  // profiled run with no name filter -- a per-kernel pass, which wants a scope per class -- keeps the per-class launches, as do
+  // float16 storage (packed tiles) and f = 64 (launch_team_chain has the reason).
   if (F == 128 && !kHalf && !prof_unfiltered()) {
     const int first[3] = {b[2], b[3], b[4]}, count[3] = {b[3] - b[2], b[4] - b[3], b[5] - b[4]};
     launch_team_chain<T>(C, F, first, count, X, Y, A0, cg_steps, "als_cg_team_chain_rows");
-  } else {
-    team(8, b[2], b[3], "als_cg_team8_rows");
-    team(4, b[3], b[4], "als_cg_team4_rows");
-    team(2, b[4], b[5], "als_cg_team2_rows");
+    const int wide_first[2] = {b[1], b[5]}, wide_count[2] = {b[2] - b[1], b[7] - b[5]};
+    launch_wide_chain<T>(C, F, wide_first, wide_count, X, Y, A0, cg_steps, "als_cg_wide_chain_rows");
+    return;
   }
+  team(16, b[1], b[2], "als_cg_team16_rows");  // (names: the row class)
+  team(8, b[2], b[3], "als_cg_team8_rows");
+  team(4, b[3], b[4], "als_cg_team4_rows");
+  team(2, b[4], b[5], "als_cg_team2_rows");
   // short rows.  f = 128: 16 rows per workgroup in lock step with the gramian product on the matrix cores (measured 1.16 ms per
   // configs[2] iteration against 1.38 ms for independent waves with the VALU product -- at f = 128 the product is 57 % of a short
   // row's arithmetic); f = 64: independent waves win (configs[1] shape: 0.84 against 0.94 ms), the product is a quarter of the size

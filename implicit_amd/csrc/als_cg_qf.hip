@@ -1,6 +1,7 @@
 // K1f: the 32-entry fp32 tile of the team kernel (als_qf_common.h has the kernel and its design) with als_cg_qfteam_kernel --
-// the mid rows of fp32 storage and the f = 64 short rows of both storages -- and the f = 128 short-row kernel
-// als_cg_qfgroup_kernel.
+// the mid rows of fp32 storage and the f = 64 short rows of both storages -- the f = 128 short-row kernel
+// als_cg_qfgroup_kernel, and the two chained launches of fp32 storage at f = 128 (als_cg_qfteam_chain_kernel,
+// als_cg_qfwide_chain_kernel).
 //
 // Arithmetic contract: the oracle's CG (implicit/cpu/_als.pyx:152-248).
 #include <type_traits>
@@ -254,25 +255,13 @@ __device__ __forceinline__ float tile_pass(f32x2 (&y)[8][F / 32], float *cw, int
   }
 }
 
-template <int F, typename ST>
-__global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__restrict__ order, int first, int count,
-                                                              const int32_t *__restrict__ indptr,
-                                                              const int32_t *__restrict__ indices,
-                                                              const float *__restrict__ data, ST *__restrict__ X,
-                                                              const ST *__restrict__ Y, const float *__restrict__ A0, int cg_steps) {
-  using Cfg = QFGroupCfg<F>;
-  constexpr int FC = F / 64, FE = F / 16, LD = Cfg::LD;
-  constexpr bool ROLL = Tile32<ST>::ROLL;
+// The short-row kernel has two parts, like a team kernel (als_qf_common.h): a workgroup prologue -- the gramian as three bf16
+// planes into LDS -- and the group loop.  The per-class kernel runs them in sequence; the chain of the two 1024-thread classes
+// (als_cg_qfwide_chain_kernel) runs them after the team-16 class, over the same allocation.
+template <int F> __device__ __forceinline__ void group_stage_gramian(const float *__restrict__ A0) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int LDB = Cfg::LDB;
-  // [A0 hi | mid | lo, bf16 F x LDB each][Pb hi | mid | lo, 16 x LDB][Ps][Outs][cws]
-  __bf16 *A0b = reinterpret_cast<__bf16 *>(smem);       // term t at A0b + t F LDB
-  __bf16 *Pb = A0b + (size_t)3 * F * LDB;               // term t at Pb + t 16 LDB
-  float *Ps = reinterpret_cast<float *>(Pb + (size_t)3 * 16 * LDB);  // [16][LD] operands (natural order)
-  float *Outs = Ps + 16 * LD;                          // [KH][16][LD]  K-slice partial products
-  float *cws = Outs + (size_t)Cfg::KH * 16 * LD;       // [16][64]  per-entry weights (gather_pair)
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  constexpr int LDB = QFGroupCfg<F>::LDB;
+  __bf16 *A0b = reinterpret_cast<__bf16 *>(smem);
   for (int e = threadIdx.x; e < F * F; e += 1024) {
     int r = e / F, c = e - r * F;
     __bf16 h, m, l;
@@ -280,6 +269,34 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
     A0b[r * LDB + c] = h, A0b[(size_t)F * LDB + r * LDB + c] = m, A0b[(size_t)2 * F * LDB + r * LDB + c] = l;
   }
   __syncthreads();
+}
+
+// The group loop: rows [first, first + count) of the schedule in groups of 16 consecutive rows, one wavefront per row.
+//   TICKETS false: a workgroup's groups are blockIdx.x + k gridDim.x -- the per-class kernel.
+//   TICKETS true : a workgroup draws its groups by ticket, by the protocol of team_rows (team_tickets.h) with the workgroup as
+//     the team and the group as the row: group k belongs to queue k mod 8, workgroup b serves queue b mod 8; with N workgroups
+//     on a queue, workgroup g starts with the tickets g, g + N, g + 2 N, g + 3 N -- the four groups the metadata pipeline holds
+//     -- and every later one is an atomic increment of *counter.  Lane 0 of wave 0 draws after the first operand of a group
+//     is published, takes the value at the end of that pass and leaves the ticket (clamped to the queue's end) in one LDS
+//     word before the barrier that ends the pass; all 16 waves read it after that barrier.  The pass chain gains no barrier,
+//     wait or poll.  A workgroup whose newest ticket is at or past the queue's end draws no more.
+template <int F, typename ST, bool TICKETS = false>
+__device__ __forceinline__ void group_rows(const int32_t *__restrict__ order, int first, int count, const int32_t *__restrict__ indptr,
+                                           const int32_t *__restrict__ indices, const float *__restrict__ data, ST *__restrict__ X,
+                                           const ST *__restrict__ Y, int cg_steps, unsigned *counter = nullptr, unsigned base = 0u) {
+  using Cfg = QFGroupCfg<F>;
+  constexpr int FC = F / 64, FE = F / 16, LD = Cfg::LD;
+  constexpr bool ROLL = Tile32<ST>::ROLL;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int LDB = Cfg::LDB;
+  // [A0 hi | mid | lo, bf16 F x LDB each][Pb hi | mid | lo, 16 x LDB][Ps][Outs][cws]([ticket word], TICKETS)
+  __bf16 *A0b = reinterpret_cast<__bf16 *>(smem);       // term t at A0b + t F LDB
+  __bf16 *Pb = A0b + (size_t)3 * F * LDB;               // term t at Pb + t 16 LDB
+  float *Ps = reinterpret_cast<float *>(Pb + (size_t)3 * 16 * LDB);  // [16][LD] operands (natural order)
+  float *Outs = Ps + 16 * LD;                          // [KH][16][LD]  K-slice partial products
+  float *cws = Outs + (size_t)Cfg::KH * 16 * LD;       // [16][64]  per-entry weights (gather_pair)
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float *prow = Ps + (size_t)wave * LD;
   float *cw = cws + (size_t)wave * 64;
   const unsigned cf = (unsigned)QL<F>::cfactor(lane, 0);  // this lane's compact slots inside a natural-order vector
@@ -351,13 +368,32 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
   // barriers and the same arithmetic.
   const bool product_first = ((wave >> 2) & 1) == 0;
 
-  const int groups = (count + 15) / 16, g_step = gridDim.x;
+  // A workgroup's groups are numbered g: the groups blockIdx.x + k gridDim.x themselves, or (TICKETS) the tickets of its queue,
+  // ticket g being group 8 g + queue.  `groups` is the end of that numbering.
+  const int queue = TICKETS ? (int)(blockIdx.x % kTicketQueues) : 0;
+  const int all_groups = (count + 15) / 16;
+  const int groups = TICKETS ? (all_groups - queue + kTicketQueues - 1) / kTicketQueues : all_groups;
+  const int g_step = TICKETS ? (int)((gridDim.x - queue + kTicketQueues - 1) / kTicketQueues) : (int)gridDim.x;
+  const int g_first = TICKETS ? (int)(blockIdx.x / kTicketQueues) : (int)blockIdx.x;
   // row of this wave in group g (groups past the end and rows past the count re-read the last row and stay invalid)
-  auto row_id = [&](int g) { return order[first + min(g * 16 + wave, count - 1)]; };  // uniform address: scalar load
-  auto row_valid = [&](int g) { return g < groups && g * 16 + wave < count; };
-  int id0 = row_id(blockIdx.x), id1 = row_id(blockIdx.x + g_step), id2 = row_id(blockIdx.x + 2 * g_step), id3 = row_id(blockIdx.x + 3 * g_step);
+  auto row_of = [&](int g) { return (TICKETS ? kTicketQueues * g + queue : g) * 16 + wave; };
+  auto row_id = [&](int g) { return order[first + min(row_of(g), count - 1)]; };  // uniform address: scalar load
+  auto row_valid = [&](int g) { return g < groups && row_of(g) < count; };
+  // TICKETS: the tickets of the three groups after the one at the top of the body, and the counter value of a draw on its way
+  int t1 = g_first + g_step, t2 = g_first + 2 * g_step, t3 = g_first + 3 * g_step;
+  unsigned drawn = 0u;
+  unsigned *ticket_word = reinterpret_cast<unsigned *>(cws + 16 * 64);
+  auto draw = [&]() {  // team_rows::draw
+    if (lane == 0) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(drawn) : "v"(counter), "v"(1u) : "memory");
+  };
+  auto take_draw = [&]() {  // wave 0, before the barrier that ends the group's first pass
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(drawn)::"memory");
+    const unsigned t = min((unsigned)__builtin_amdgcn_readfirstlane(drawn) - base + 4u * (unsigned)g_step, (unsigned)groups);
+    if (lane == 0) *ticket_word = t;
+  };
+  int id0 = row_id(g_first), id1 = row_id(t1), id2 = row_id(t2), id3 = row_id(t3);
   int b0 = indptr[id0], e0 = indptr[id0 + 1], b1 = indptr[id1], e1 = indptr[id1 + 1], b2 = indptr[id2], e2 = indptr[id2 + 1];
-  int ent_col, ent_cnt = row_valid(blockIdx.x) ? e0 - b0 : 0;
+  int ent_col, ent_cnt = row_valid(g_first) ? e0 - b0 : 0;
   float ent_c;
   fetch_entries(indices, data, opaque(lane), b0, max(e0, b0 + 1), ent_col, ent_c);
   bool tile_ready = false;
@@ -369,8 +405,9 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
     for (int cc = 0; cc < FC; ++cc) v[cc] = 0.f;
   };
   kill(x);
-  for (int g = blockIdx.x; g < groups; g += g_step) {
+  for (int g = g_first; g < groups;) {
     const bool valid = row_valid(g);
+    int t_new = t3 + g_step;  // TICKETS: the ticket drawn during this group, or the queue's end
     ST *xrow = X + (size_t)id0 * F;
     if (!tile_ready) {  // first group, or this wave's previous row ended before its last pass
       cnt = ent_cnt;
@@ -380,20 +417,32 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
         constexpr int P = decltype(Pc)::value;
         if (8 * P < cnt) gather_pair<Tile32<ST>, F, P>(y, cw, ent_col, ent_c, cnt, Y, lane);
       });
-      ent_cnt = row_valid(g + g_step) ? e1 - b1 : 0;
+      ent_cnt = row_valid(t1) ? e1 - b1 : 0;
       fetch_entries(indices, data, opaque(lane), b1, max(e1, b1 + 1), ent_col, ent_c);
       load_compact<F>(xrow, opaque(lane), x);
     }
-    // ent_* now describe this wave's row of group g + g_step
+    // ent_* now describe this wave's row of the next group (t1)
     float xc[FC], r[FC], p[FC], Ap[FC], sp[FC];
 #pragma unroll
     for (int cc = 0; cc < FC; ++cc) xc[cc] = x[cc];
     // r = -(A0 x) + sum_k (c+ - (|c|-1) y.x) y        (_als.pyx:187-201)
     publish(xc, valid);
+    const bool drawing = TICKETS && t3 < groups;  // uniform over the workgroup
+    if constexpr (TICKETS) {
+      // nothing else of wave 0 is in flight here: the iterate it has just published was its newest load
+      if (drawing && wave == 0) draw();
+    }
     if (!product_first) tile_pass<F, true, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
     product();
     if (product_first) tile_pass<F, true, false, false, ST>(y, cw, cnt, prow, sp, lane, 0, ent_col, ent_c, Y);
+    if constexpr (TICKETS) {
+      if (drawing && wave == 0) take_draw();
+    }
     __syncthreads();
+    if constexpr (TICKETS) {
+      // the word is written again only after the next group's first barrier, which every wave reaches after this read
+      t_new = drawing ? (int)__builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile unsigned *>(ticket_word)) : groups;
+    }
     collect(Ap);
 #pragma unroll
     for (int cc = 0; cc < FC; ++cc) p[cc] = r[cc] = sp[cc] - Ap[cc];
@@ -446,7 +495,7 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
       if (active) {
         if constexpr (ROLL) {
           cnt = ent_cnt;
-          ent_cnt = row_valid(g + 2 * g_step) ? e2 - b2 : 0;
+          ent_cnt = row_valid(t2) ? e2 - b2 : 0;
           fetch_entries(indices, data, opaque(lane), b2, max(e2, b2 + 1), ent_col, ent_c);
           load_compact<F>(X + (size_t)id1 * F, opaque(lane), x);
           rolled = true;
@@ -465,9 +514,20 @@ __global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__r
     }
     if (store) store_compact<F>(xrow, opaque(lane), xc);
     tile_ready = rolled;
-    id0 = id1, id1 = id2, id2 = id3, id3 = row_id(g + 4 * g_step);
+    g = t1, t1 = t2, t2 = t3, t3 = t_new;
+    id0 = id1, id1 = id2, id2 = id3, id3 = row_id(t3);
     b0 = b1, e0 = e1, b1 = b2, e1 = e2, b2 = indptr[id2], e2 = indptr[id2 + 1];
   }
+}
+
+template <int F, typename ST>
+__global__ __launch_bounds__(1024) void als_cg_qfgroup_kernel(const int32_t *__restrict__ order, int first, int count,
+                                                              const int32_t *__restrict__ indptr,
+                                                              const int32_t *__restrict__ indices,
+                                                              const float *__restrict__ data, ST *__restrict__ X,
+                                                              const ST *__restrict__ Y, const float *__restrict__ A0, int cg_steps) {
+  group_stage_gramian<F>(A0);
+  group_rows<F, ST>(order, first, count, indptr, indices, data, X, Y, cg_steps);
 }
 
 template <typename T>
@@ -483,6 +543,100 @@ static void launch_qfgroup(const imp_csr *C, int first, int count, T *X, const T
                                       cg_steps);
   IMP_CHECK_HIP(hipGetLastError());
 }
+
+// ---- the two 1024-thread classes in one persistent launch ----------------------------------------------------------------
+// (256,512] -- a team of 16 wavefronts per row -- and the short rows both hold a CU with one workgroup.  As two launches on a
+// grid of two workgroups per CU every CU staged the gramian twice per class (for the short rows: 16 K values split into three
+// bf16 planes), started its pipelines twice and idled in two tails.  Here the grid is exactly the resident workgroups; a
+// workgroup runs team-16 rows by ticket (team_rows, TICKETS, one team per workgroup), then -- after one barrier -- re-stages the
+// gramian as bf16 planes over the same allocation and runs groups of short rows by ticket (group_rows, TICKETS).  The ticket
+// bookkeeping is WideTickets (team_tickets.h).  Every row's arithmetic is that of its class kernel.
+//
+// IMP_WIDE_FORM (compile time, A/B builds): 0 the chain with tickets in both classes; 1 the chain with the short rows' groups
+// dealt in fixed strides over the resident grid; 2 no chain: each class in a launch of its own on the resident grid, with tickets.
+#ifndef IMP_WIDE_FORM
+#define IMP_WIDE_FORM 0
+#endif
+struct WideClassArgs {
+  int first[WideTickets::kClasses], count[WideTickets::kClasses];  // rows
+  unsigned base[WideTickets::kClasses][WideTickets::kQueues];
+};
+static_assert(WideTickets::kQueues == kTicketQueues && WideTickets::kGroupRows == 16, "queues and groups of the ticketed classes");
+// the larger of the two layouts; the short rows' ticket word follows theirs
+template <int F> constexpr size_t wide_chain_lds_bytes() {
+  return std::max(team_lds_bytes<F, 16, 1024, 32>(), QFGroupCfg<F>::lds_bytes + 16);
+}
+template <int F, typename ST, bool SHORT_TICKETS>
+__global__ __launch_bounds__(1024) void als_cg_qfwide_chain_kernel(const int32_t *__restrict__ order, WideClassArgs cls,
+                                                                   unsigned *__restrict__ counters,
+                                                                   const int32_t *__restrict__ indptr,
+                                                                   const int32_t *__restrict__ indices,
+                                                                   const float *__restrict__ data, ST *__restrict__ X,
+                                                                   const ST *__restrict__ Y, const float *__restrict__ A0,
+                                                                   int cg_steps) {
+  const unsigned queue = blockIdx.x % kTicketQueues;
+  if (cls.count[0] > 0)  // uniform over the grid
+    team_rows<Tile32<ST>, F, 16, 1024, true, true>(order, cls.first[0], cls.count[0], indptr, indices, data, X, Y, A0, cg_steps,
+                                                   counters + queue * WideTickets::kCounterStride, cls.base[0][queue]);
+  if (cls.count[1] > 0) {
+    if (cls.count[0] > 0) __syncthreads();  // every wavefront has left the team layout
+    group_stage_gramian<F>(A0);
+    group_rows<F, ST, SHORT_TICKETS>(order, cls.first[1], cls.count[1], indptr, indices, data, X, Y, cg_steps,
+                                     counters + (kTicketQueues + queue) * WideTickets::kCounterStride, cls.base[1][queue]);
+  }
+}
+
+template <typename T>
+void launch_wide_chain(const imp_csr *C, int f, const int (&first)[2], const int (&count)[2], T *X, const T *Y, const float *A0, int cg_steps,
+                       const char *name) {
+  if constexpr (std::is_same<T, float>::value) {
+    if (f != 128) throw std::invalid_argument("launch_wide_chain: f must be 128");
+    constexpr int F = 128;
+    constexpr bool kShortTickets = IMP_WIDE_FORM != 1;
+    if (count[0] <= 0 && count[1] <= 0) return;
+    const size_t lds = wide_chain_lds_bytes<F>();
+    auto kern = als_cg_qfwide_chain_kernel<F, T, kShortTickets>;
+    // the resident workgroups per CU, asked of the runtime once per process (registers and LDS allow one)
+    static const int per_cu = [&] {
+      int n = 0;
+      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      IMP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(kern), 1024, lds));
+      if (n < 1) throw std::runtime_error("launch_wide_chain: the kernel does not fit a compute unit");
+      return n;
+    }();
+    IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int grid = std::max(ctx().num_cus * per_cu, WideTickets::kQueues);  // every queue needs a workgroup
+    for (int c = 0; c < 2; ++c)
+      if (count[c] >= WideTickets::kMaxCount) throw std::invalid_argument("launch_wide_chain: too many rows in a class");
+    Context &cx = ctx();
+    if (!cx.wide_counters.data())  // zeroed once, on the library stream
+      cx.wide_counters.alloc((size_t)WideTickets::kClasses * WideTickets::kQueues * WideTickets::kCounterStride, true);
+    // one launch of the classes in `on`
+    auto run = [&](bool on0, bool on1) {
+      WideClassArgs cls;
+      const int32_t rows[2] = {on0 ? std::max(count[0], 0) : 0, on1 ? std::max(count[1], 0) : 0};
+      if (rows[0] == 0 && rows[1] == 0) return;
+      for (int c = 0; c < 2; ++c) cls.first[c] = first[c], cls.count[c] = rows[c];
+      WideTickets after = cx.wide_tickets;
+      // (fixed strides draw nothing: the bases of the short rows are not used and must not move)
+      const int32_t ticketed[2] = {rows[0], kShortTickets ? rows[1] : 0};
+      after.launch_rows(ticketed, grid, cls.base);
+      kern<<<grid, 1024, lds, stream()>>>(C->order.data(), cls, cx.wide_counters.data(), C->indptr.data(), C->indices.data(),
+                                         C->data.data(), X, Y, A0, cg_steps);
+      IMP_CHECK_HIP(hipGetLastError());
+      cx.wide_tickets = after;  // a launch that was not queued draws nothing
+    };
+    IMP_PROF(name);
+    if (IMP_WIDE_FORM == 2) run(true, false), run(false, true);
+    else run(true, true);
+  } else {
+    throw std::invalid_argument("launch_wide_chain: fp32 storage only");
+  }
+}
+template void launch_wide_chain<float>(const imp_csr *, int, const int (&)[2], const int (&)[2], float *, const float *, const float *, int,
+                                       const char *);
+template void launch_wide_chain<__half>(const imp_csr *, int, const int (&)[2], const int (&)[2], __half *, const __half *, const float *,
+                                        int, const char *);
 
 template <typename T>
 void launch_group_fused(const imp_csr *C, int f, int first, int count, T *X, const T *Y, const float *A0, int cg_steps, const char *name) {

@@ -214,6 +214,8 @@ struct Context {
   DeviceArray<unsigned> nm_fix_rows;             // rows the normal-matrix kernels left to the fix-up kernel (operands beyond the fp16 range)
   DeviceArray<unsigned> chain_counters;          // ticket counters of the chained mid-row classes, zeroed once and never reset (als_cg_qf.hip)
   ChainTickets chain_tickets;                    // what those counters read after everything queued so far (team_tickets.h)
+  DeviceArray<unsigned> wide_counters;           // the same for the chained 1024-thread classes (launch_wide_chain)
+  WideTickets wide_tickets;
   DeviceArray<int> nm_ticket;                    // work counter of the normal-matrix kernel (als_cg_nm.hip), reset by every launch
   DeviceArray<unsigned long long> bpr_stats;     // correct / skipped counts and the id check's violation bits of bpr_update (bpr.hip)
   DeviceArray<float> lmf_ws;                     // partial sums of the long rows' segments of lmf_update (lmf.hip)

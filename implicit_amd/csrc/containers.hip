@@ -606,6 +606,29 @@ int imp_host_chain_tickets(uint32_t *next, const int32_t *count, int32_t workgro
   });
 }
 
+// The same for the chained 1024-thread launch (launch_wide_chain): next[2][8], rows[2] = rows of (256,512] and short rows; the
+// short rows are ticketed in groups of 16.
+int imp_host_wide_tickets(uint32_t *next, const int32_t *rows, int32_t workgroups, uint32_t *base, uint32_t *draws) {
+  return guarded_host([&] {
+    constexpr int NC = WideTickets::kClasses, NQ = WideTickets::kQueues;
+    WideTickets t;
+    uint32_t b[NC][NQ];
+    if (workgroups <= 0) throw std::invalid_argument("host_wide_tickets: the grid holds at least one workgroup");
+    for (int k = 0; k < NC; ++k) {
+      if (rows[k] < 0 || rows[k] >= WideTickets::kMaxCount)
+        throw std::invalid_argument("host_wide_tickets: a class holds 0 .. 2^30 - 1 rows");
+      for (int q = 0; q < NQ; ++q) t.next[k][q] = next[k * NQ + q];
+    }
+    const int32_t r[NC] = {rows[0], rows[1]};
+    t.launch_rows(r, workgroups, b);
+    for (int k = 0; k < NC; ++k)
+      for (int q = 0; q < NQ; ++q) {
+        draws[k * NQ + q] = t.next[k][q] - next[k * NQ + q];
+        next[k * NQ + q] = t.next[k][q], base[k * NQ + q] = b[k][q];
+      }
+  });
+}
+
 // ---- Matrix -------------------------------------------------------------------------------------
 int imp_matrix_create(size_t rows, size_t cols, const void *host_data, size_t itemsize, imp_matrix **out) {
   return guarded([&] {

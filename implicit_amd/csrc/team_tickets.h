@@ -1,5 +1,6 @@
-// Ticket bookkeeping of the chained mid-row CG launch (als_cg_qfteam_chain_kernel, als_cg_qf.hip): pure host arithmetic (no
-// device code, no HIP header), so that it can be read and tested without a GPU (imp_host_chain_tickets).
+// Ticket bookkeeping of the chained CG launches (als_cg_qfteam_chain_kernel and als_cg_qfwide_chain_kernel, als_cg_qf.hip): pure
+// host arithmetic (no device code, no HIP header), so that it can be read and tested without a GPU (imp_host_chain_tickets,
+// imp_host_wide_tickets).
 //
 // Inside a class of the chain the teams draw their rows by ticket.  One counter for a whole class does not work: every row
 // of the device would add to one address, and atomics on one address are served one after the other (measured: 150 K draws
@@ -25,8 +26,9 @@
 
 namespace imp {
 
-struct ChainTickets {
-  static constexpr int kClasses = 3;               // team widths 8, 4, 2
+// NC classes in one launch: ChainTickets (below) for the three 512-thread classes, WideTickets for the two 1024-thread ones
+template <int NC> struct TicketClasses {
+  static constexpr int kClasses = NC;
   static constexpr int kQueues = 8;                // queues per class
   static constexpr int kCounterStride = 64;        // words between two device counters: a cache line of their own each
   static constexpr int32_t kMaxCount = 1 << 30;    // a ticket travels in the upper 30 bits of a team's control word
@@ -53,6 +55,21 @@ struct ChainTickets {
         base[c][q] = next[c][q];
         next[c][q] += draws(queue_rows(count[c], q), queue_workgroups(workgroups, q) * teams_per_workgroup[c]);  // modulo 2^32
       }
+  }
+};
+
+typedef TicketClasses<3> ChainTickets;  // team widths 8, 4, 2 (als_cg_qfteam_chain_kernel)
+
+// The chained 1024-thread classes (als_cg_qfwide_chain_kernel): class 0 is (256,512], a team of 16 wavefronts -- the workgroup
+// -- per row; class 1 are the short rows, whose ticketed unit is a GROUP of kGroupRows consecutive schedule rows that a
+// workgroup solves in lock step.  Both have one team per workgroup, and the protocol above holds with "row" read as "group".
+struct WideTickets : TicketClasses<2> {
+  static constexpr int kGroupRows = 16;
+  static int32_t groups(int32_t rows) { return rows > 0 ? (rows + kGroupRows - 1) / kGroupRows : 0; }
+  // rows[0]: rows of (256,512], rows[1]: short rows
+  void launch_rows(const int32_t (&rows)[2], int32_t workgroups, uint32_t (&base)[2][kQueues]) {
+    const int32_t units[2] = {rows[0], groups(rows[1])}, teams[2] = {1, 1};
+    launch(units, workgroups, teams, base);
   }
 };
 

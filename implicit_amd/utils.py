@@ -197,3 +197,16 @@ def chain_tickets(state, counts, workgroups, teams_per_workgroup=(1, 2, 4)):
     check(lib().imp_host_chain_tickets(state.ctypes.data, counts.ctypes.data, int(workgroups), teams.ctypes.data, base.ctypes.data,
                                        draws.ctypes.data))
     return base, draws
+
+
+def wide_tickets(state, rows, workgroups):
+    """The same for the chained 1024-thread CG classes (imp_host_wide_tickets): `state` is uint32 [2, 8]; `rows` holds the rows
+    of (256,512] and the short rows, which are ticketed in groups of 16.  Returns (base, draws), [2, 8] each."""
+    from .gpu._hip import check, lib
+
+    assert state.dtype == np.uint32 and state.shape == (2, 8) and state.flags.c_contiguous
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    assert rows.shape == (2,)
+    base, draws = np.empty((2, 8), np.uint32), np.empty((2, 8), np.uint32)
+    check(lib().imp_host_wide_tickets(state.ctypes.data, rows.ctypes.data, int(workgroups), base.ctypes.data, draws.ctypes.data))
+    return base, draws

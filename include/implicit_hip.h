@@ -114,6 +114,11 @@ int imp_host_csr_plan(int32_t rows, int32_t cols, const int32_t *indptr, const i
 int imp_host_chain_tickets(uint32_t *next, const int32_t *count, int32_t workgroups, const int32_t *teams_per_workgroup, uint32_t *base,
                            uint32_t *draws);
 
+/* Host code, no device involved: the same for the chained 1024-thread CG classes -- (256,512], one 16-wavefront team per row, and
+ * the short rows, ticketed in groups of 16 consecutive schedule rows; one team per workgroup in both.  next[2][8], rows[2]
+ * (0 .. 2^30 - 1 each), workgroups (> 0); outputs base[2][8] and draws[2][8]. */
+int imp_host_wide_tickets(uint32_t *next, const int32_t *rows, int32_t workgroups, uint32_t *base, uint32_t *draws);
+
 /* ---- Matrix (matrix.h:23-90, matrix.cu:34-220) -------------------------------------------- */
 /* Matrix(rows, cols, data, allocate=true, itemsize): allocates; copies rows*cols*itemsize bytes
  * from host_data when non-NULL, zero-fills otherwise (matrix.cu:80-96). */
