@@ -26,13 +26,15 @@
 // on the sample path.  The negative check is a G-ary search: the group's lanes load G splitters of the row, a ballot
 // narrows the range to one of G slices -- ceil(log_G(deg)) dependent loads instead of log2(deg).  The ids of a group's
 // next sample are loaded while the current one is searched and updated.  The number of samples in flight is capped by the
-// matrix size (see the launch): Hogwild only works while concurrent samples seldom share a row.
+// matrix size (see the launch): Hogwild only works while concurrent samples seldom share a row.  The search, the count
+// reduction, the dispatch over CPL and the cap live in pair_sgd.h, shared with the WARP kernel (warp.hip).
 //
 // Every id the update kernel turns into an address has been checked on the device first (bpr_check_kernel): an id
 // outside its matrix returns IMP_OUT_OF_RANGE with nothing launched -- an out-of-bounds write is a device fault.
 #include <cstdlib>
 
 #include "common.h"
+#include "pair_sgd.h"
 #include "philox.h"
 #include "wave_ops.h"
 
@@ -63,7 +65,7 @@ template <int G, int CPL>
 __global__ __launch_bounds__(256) void bpr_update_kernel(BprArgs a) {
   const int lane = threadIdx.x & 63;
   const int gl = lane & (G - 1);  // lane inside the group
-  const uint64_t gmask = G == 64 ? ~0ull : ((1ull << G) - 1) << (lane & ~(G - 1));
+  const uint64_t gmask = group_mask<G>(lane);
   const int64_t ngroups = (int64_t)gridDim.x * (blockDim.x / G);
   const int C = a.C;
   const float lr = a.lr, reg = a.reg;
@@ -77,24 +79,8 @@ __global__ __launch_bounds__(256) void bpr_update_kernel(BprArgs a) {
     int un = 0, in = 0, jn = 0;
     if (s + ngroups < a.samples) bpr_draw(a, s + ngroups, un, in, jn);
 
-    bool skip = false;
-    if (a.verify) {
-      int64_t lo = a.indptr[u], hi = a.indptr[u + 1];
-      while (hi - lo > G) {  // group-uniform trip count
-        const int64_t step = (hi - lo + G - 1) / G;
-        const int64_t p = lo + gl * step;
-        // lanes whose splitter is <= j form a prefix of the group (sorted row): the answer lies in slice k-1
-        const int k = __popcll(__builtin_amdgcn_ballot_w64(p < hi && a.itemids[p] <= j) & gmask);
-        if (k == 0) {
-          hi = lo;  // j precedes the whole row
-          break;
-        }
-        lo += (int64_t)(k - 1) * step;
-        hi = lo + step < hi ? lo + step : hi;
-      }
-      const int64_t p = lo + gl;
-      skip = (__builtin_amdgcn_ballot_w64(p < hi && a.itemids[p] == j) & gmask) != 0;
-    }
+    // the negative check (pair_sgd.h): is j in row u of the pattern
+    const bool skip = a.verify && group_row_contains<G>(a.itemids, a.indptr[u], a.indptr[u + 1], j, gl, gmask);
 
     if (skip) {
       skipped += gl == 0;
@@ -132,23 +118,7 @@ __global__ __launch_bounds__(256) void bpr_update_kernel(BprArgs a) {
     u = un, i = in, j = jn;
   }
 
-  // counts: wave sum, then one atomic per workgroup
-  for (int o = 32; o > 0; o >>= 1) {
-    correct += __shfl_xor(correct, o);
-    skipped += __shfl_xor(skipped, o);
-  }
-  __shared__ unsigned long long red[2];
-  if (threadIdx.x == 0) red[0] = red[1] = 0;
-  __syncthreads();
-  if (lane == 0) {
-    atomicAdd(&red[0], (unsigned long long)correct);
-    atomicAdd(&red[1], (unsigned long long)skipped);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(&a.stats[0], red[0]);
-    atomicAdd(&a.stats[1], red[1]);
-  }
+  block_add_counts(correct, skipped, a.stats);
 }
 
 // The pre-pass: 0 <= userids < x_rows, 0 <= itemids < y_rows, 0 <= indptr <= nnz.  Violations OR bits 1 / 2 / 4 into *bad.
@@ -179,7 +149,7 @@ __global__ __launch_bounds__(256) void bpr_check_kernel(const int32_t *__restric
 
 // lanes per sample: the narrowest group that keeps a row in at most 8 registers per lane (more samples per wave in flight),
 // IMP_BPR_LANES=16/32/64 overrides it for measurement where C <= 16 x lanes
-static int bpr_group(int C) {
+int bpr_group(int C) {
   if (const char *e = std::getenv("IMP_BPR_LANES")) {
     const int g = std::atoi(e);
     if ((g == 16 || g == 32 || g == 64) && C <= 16 * g) return g;
@@ -188,15 +158,28 @@ static int bpr_group(int C) {
 }
 
 template <int G> static void launch_bpr(const BprArgs &a, int grid) {
-  const int cpl = (a.C + G - 1) / G;
-  if (cpl <= 1) bpr_update_kernel<G, 1><<<grid, 256, 0, stream()>>>(a);
-  else if (cpl <= 2) bpr_update_kernel<G, 2><<<grid, 256, 0, stream()>>>(a);
-  else if (cpl <= 3) bpr_update_kernel<G, 3><<<grid, 256, 0, stream()>>>(a);
-  else if (cpl <= 4) bpr_update_kernel<G, 4><<<grid, 256, 0, stream()>>>(a);
-  else if (cpl <= 6) bpr_update_kernel<G, 6><<<grid, 256, 0, stream()>>>(a);
-  else if (cpl <= 8) bpr_update_kernel<G, 8><<<grid, 256, 0, stream()>>>(a);
-  else if (cpl <= 12) bpr_update_kernel<G, 12><<<grid, 256, 0, stream()>>>(a);
-  else bpr_update_kernel<G, 16><<<grid, 256, 0, stream()>>>(a);
+  for_columns_per_lane((a.C + G - 1) / G, [&](auto cpl) { bpr_update_kernel<G, decltype(cpl)::value><<<grid, 256, 0, stream()>>>(a); });
+}
+
+void check_pair_ids(const char *who, const char *prof, const imp_intvector *userids, const imp_intvector *itemids,
+                    const imp_intvector *indptr, size_t x_rows, size_t y_rows, unsigned long long *bad_word) {
+  const int64_t nnz = (int64_t)userids->size;
+  {
+    IMP_PROF(prof);
+    const int64_t work = std::max(nnz / 4, (int64_t)indptr->size);
+    const int grid = (int)std::min<int64_t>((work + 255) / 256, ctx().num_cus * 8);
+    const bool aligned = ((uintptr_t)userids->v.data() | (uintptr_t)itemids->v.data()) % 16 == 0;
+    bpr_check_kernel<<<grid, 256, 0, stream()>>>(userids->v.data(), itemids->v.data(), nnz, aligned ? nnz / 4 : 0, indptr->v.data(),
+                                                 (int64_t)indptr->size, (int64_t)x_rows, (int64_t)y_rows, bad_word);
+    IMP_CHECK_HIP(hipGetLastError());
+  }
+  unsigned long long bad = 0;
+  IMP_CHECK_HIP(hipMemcpyAsync(&bad, bad_word, sizeof(bad), hipMemcpyDeviceToHost, stream()));
+  sync();
+  const std::string w(who);
+  if (bad & 1) throw out_of_range_error(w + ": a user id is outside [0, X.rows)");
+  if (bad & 2) throw out_of_range_error(w + ": an item id is outside [0, Y.rows)");
+  if (bad & 4) throw out_of_range_error(w + ": an indptr entry is outside [0, nnz]");
 }
 
 }  // namespace imp
@@ -220,26 +203,12 @@ extern "C" int imp_bpr_update(const imp_intvector *userids, const imp_intvector 
     *correct = *skipped = 0;
     if (nnz == 0 || n == 0) return;
 
-    auto &st = ctx().bpr_stats;
+    auto &st = ctx().pair_stats;
     if (st.size < 3) st.alloc(3);
     unsigned long long *stats = st.data();
     IMP_CHECK_HIP(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), stream()));
     const int cap = ctx().num_cus * 8;  // 8 workgroups of 4 waves per CU: the most the CU holds
-    {
-      IMP_PROF("bpr_check_ids");
-      const int64_t work = std::max(nnz / 4, (int64_t)indptr->size);
-      const int grid = (int)std::min<int64_t>((work + 255) / 256, cap);
-      const bool aligned = ((uintptr_t)userids->v.data() | (uintptr_t)itemids->v.data()) % 16 == 0;
-      bpr_check_kernel<<<grid, 256, 0, stream()>>>(userids->v.data(), itemids->v.data(), nnz, aligned ? nnz / 4 : 0, indptr->v.data(),
-                                                   (int64_t)indptr->size, (int64_t)X->rows, (int64_t)Y->rows, stats + 2);
-      IMP_CHECK_HIP(hipGetLastError());
-    }
-    unsigned long long bad = 0;
-    IMP_CHECK_HIP(hipMemcpyAsync(&bad, stats + 2, sizeof(bad), hipMemcpyDeviceToHost, stream()));
-    sync();
-    if (bad & 1) throw out_of_range_error("bpr_update: a user id is outside [0, X.rows)");
-    if (bad & 2) throw out_of_range_error("bpr_update: an item id is outside [0, Y.rows)");
-    if (bad & 4) throw out_of_range_error("bpr_update: an indptr entry is outside [0, nnz]");
+    check_pair_ids("bpr_update", "bpr_check_ids", userids, itemids, indptr, X->rows, Y->rows, stats + 2);
 
     note_device_write(X->data, X->bytes());  // cached top-k planes and padded copies made from X or Y are stale after this
     note_device_write(Y->data, Y->bytes());
@@ -248,10 +217,7 @@ extern "C" int imp_bpr_update(const imp_intvector *userids, const imp_intvector 
     {
       IMP_PROF("bpr_update");
       const int G = bpr_group(a.C);
-      // samples in flight: at most min(users, items) / 16 (at least 16).  Hogwild needs concurrent samples to collide
-      // rarely; on a small matrix a full device of samples (32 K groups) would overwrite each row's updates dozens of
-      // times per round and the model stops learning.  From about 500 K rows on, the device is full anyway.
-      const int64_t in_flight = std::min<int64_t>(n, std::max<int64_t>(16, (int64_t)std::min(X->rows, Y->rows) / 16));
+      const int64_t in_flight = hogwild_in_flight(n, X->rows, Y->rows);  // the cap on concurrent samples: pair_sgd.h
       const int grid = (int)std::min<int64_t>((in_flight * G + 255) / 256, cap);
       if (G == 16) launch_bpr<16>(a, grid);
       else if (G == 32) launch_bpr<32>(a, grid);

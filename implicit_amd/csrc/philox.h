@@ -1,7 +1,8 @@
 // Counter-based Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), shared by the
-// device RandomState (random.hip), the BPR sampler (bpr.hip) and the LMF negatives (lmf.hip).  A draw is a pure function
+// device RandomState (random.hip), the BPR and WARP samplers (bpr.hip, warp.hip) and the LMF negatives (lmf.hip).  A draw is a pure function
 // of (counter, key), so a kernel's random stream does not depend on its launch geometry.  The fourth counter word tags the user:
 //   0  RandomState::uniform    1  RandomState::randn    2  bpr_update sample pairs    3  lmf_update negatives
+//   4  warp_update positives and candidates
 #ifndef IMPLICIT_AMD_CSRC_PHILOX_H_
 #define IMPLICIT_AMD_CSRC_PHILOX_H_
 #include <hip/hip_runtime.h>

@@ -12,7 +12,7 @@ HAS_RMM = False
 try:
     from ._cuda import (COOMatrix, Comm, CSRMatrix, IntVector, IVFIndex, KnnQuery, LeastSquaresSolver, Matrix,  # noqa: F401
                         Profiler, RandomState, RankingMetrics, SpMat, bpr_epoch, bpr_update, calculate_norms, core_clock_mhz, debug_occupy, fixup_rows, get_device, get_device_count, get_oversubscribe, host_ranking_metrics, lmf_update, release_workspaces,
-                        set_deferred_sync, set_device, set_oversubscribe, sparse_topk_product, synchronize)
+                        set_deferred_sync, set_device, set_oversubscribe, sparse_topk_product, synchronize, warp_epoch)
     from ._hip import lib as _lib
 
     _lib()  # ImportError when libimplicit_hip.so has not been built

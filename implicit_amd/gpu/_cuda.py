@@ -455,6 +455,28 @@ def bpr_epoch(userids, itemids, indptr, X, Y, learning_rate, regularization, see
     return correct.value, skipped.value
 
 
+def warp_epoch(userids, itemids, indptr, X, Y, learning_rate, regularization, seed, max_sampled=10, samples=None):
+    """NEW: one SGD pass of WARP-loss matrix factorization (imp_warp_update, warp.hip), returns (satisfied, trials).  The
+    arrays and matrices are those of bpr_epoch (row indices sorted); `samples`: the number of sampled positives, None for one
+    epoch (nnz).  Every positive meets up to `max_sampled` (1 .. 4096) uniformly drawn items; the first that scores within
+    1 of the positive ends the sample with a step weighted by the rank estimate; `satisfied` counts the samples that found
+    none, `trials` the draws consumed.  X / Y are updated in place.  Positives and candidates are Philox streams of (seed,
+    sample index).  Bad arguments raise ValueError, an id outside its matrix IndexError before anything is written."""
+    for name, v in (("userids", userids), ("itemids", itemids), ("indptr", indptr)):
+        if not isinstance(v, IntVector):
+            raise TypeError(f"warp_epoch: {name} must be an implicit_amd.gpu.IntVector")
+    if not isinstance(X, Matrix) or not isinstance(Y, Matrix):
+        raise TypeError("warp_epoch: X and Y must be implicit_amd.gpu.Matrix objects")
+    max_sampled = int(max_sampled)
+    if not 1 <= max_sampled <= 4096:
+        raise ValueError("warp_epoch: max_sampled must lie in 1 .. 4096")
+    satisfied, trials = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().imp_warp_update(userids._h, itemids._h, indptr._h, X._h, Y._h, float(learning_rate), float(regularization),
+                                int(seed), max_sampled, -1 if samples is None else int(samples),
+                                ctypes.byref(satisfied), ctypes.byref(trials)))
+    return satisfied.value, trials.value
+
+
 def lmf_update(cui, X, Y, deriv_sum_sq, learning_rate, regularization, neg_prop, seed, one_col=-1):
     """One Adagrad half-sweep of Logistic Matrix Factorization (imp_lmf_update, lmf.hip): X is updated in place against
     the read-only Y over the CSRMatrix `cui` (rows of X x rows of Y, values = confidences), deriv_sum_sq (the shape of X)

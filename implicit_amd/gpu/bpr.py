@@ -23,6 +23,25 @@ from .matrix_factorization_base import MatrixFactorizationBase
 log = logging.getLogger("implicit_amd")
 
 
+def initial_bias_factors(model, rs, user_items, user_counts):
+    """Sets the factors `model` does not have yet (implicit/gpu/bpr.py:99-128): items before users, (U[0, 1) - 0.5) / factors
+    over factors + 1 columns, zero rows for items and users without a nonzero, the user bias column 1.0.  Shared by the
+    pairwise models (BPR here, WARP in warp.py)."""
+    users, items = user_items.shape
+    if model.item_factors is None:
+        item_factors = rs.random((items, model.factors + 1), "float32") - 0.5
+        item_factors /= model.factors
+        item_counts = np.bincount(user_items.indices, minlength=items)
+        item_factors[item_counts == 0] = np.zeros(model.factors + 1)
+        model.item_factors = gpu.Matrix(item_factors)
+    if model.user_factors is None:
+        user_factors = rs.random((users, model.factors + 1), "float32") - 0.5
+        user_factors /= model.factors
+        user_factors[user_counts == 0] = np.zeros(model.factors + 1)
+        user_factors[:, model.factors] = 1.0
+        model.user_factors = gpu.Matrix(user_factors)
+
+
 class BayesianPersonalizedRanking(MatrixFactorizationBase):
     """Bayesian Personalized Ranking (Rendle et al., "BPR: Bayesian Personalized Ranking from Implicit Feedback").
 
@@ -43,21 +62,6 @@ class BayesianPersonalizedRanking(MatrixFactorizationBase):
         self.verify_negative_samples = verify_negative_samples
         self.random_state = random_state
 
-    def _initial_factors(self, rs, user_items, user_counts):
-        users, items = user_items.shape
-        if self.item_factors is None:
-            item_factors = rs.random((items, self.factors + 1), "float32") - 0.5
-            item_factors /= self.factors
-            item_counts = np.bincount(user_items.indices, minlength=items)
-            item_factors[item_counts == 0] = np.zeros(self.factors + 1)
-            self.item_factors = gpu.Matrix(item_factors)
-        if self.user_factors is None:
-            user_factors = rs.random((users, self.factors + 1), "float32") - 0.5
-            user_factors /= self.factors
-            user_factors[user_counts == 0] = np.zeros(self.factors + 1)
-            user_factors[:, self.factors] = 1.0
-            self.user_factors = gpu.Matrix(user_factors)
-
     def fit(self, user_items, show_progress=True, callback=None):
         """Trains on a (users x items) CSR matrix; every nonzero is a positive, its value is ignored.  `callback(epoch,
         elapsed, correct, skipped)` after every epoch."""
@@ -74,7 +78,7 @@ class BayesianPersonalizedRanking(MatrixFactorizationBase):
         user_counts = np.ediff1d(indptr)
         userids = np.repeat(np.arange(users, dtype=np.int32), user_counts)
 
-        self._initial_factors(rs, user_items, user_counts)
+        initial_bias_factors(self, rs, user_items, user_counts)
         self._item_norms = self._user_norms = None
         self._item_norms_host = self._user_norms_host = None
 

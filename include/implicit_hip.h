@@ -266,6 +266,20 @@ int imp_bpr_update(const imp_intvector *userids, const imp_intvector *itemids, c
                    imp_matrix *Y, float learning_rate, float regularization, int64_t seed, int verify_negative, int64_t samples,
                    int64_t *correct, int64_t *skipped);
 
+/* ---- WARP training (no reference counterpart: Weston et al., "WSABIE") ------------------------------------------------- */
+/* One SGD pass of WARP-loss matrix factorization over `samples` sampled positives (samples < 0: nnz, one epoch).  userids,
+ * itemids, indptr, X, Y: as imp_bpr_update, row indices sorted.  Each positive (u, i) meets up to max_sampled (1 .. 4096)
+ * uniformly drawn items j; a draw the user has liked is consumed without effect; the first j with X[u].Y[j] > X[u].Y[i] - 1
+ * ends the sample with an SGD step weighted by min(10, log(max(1, (items - 1) / trials used))).  The positives and the
+ * candidates are counter-based Philox streams of (seed, sample index): warp.hip states the contract in full.  *satisfied:
+ * samples without a violating draw (nothing written for them); *trials: draws consumed over all samples.  Synchronous,
+ * deferred mode included.  Ids are checked on the device first: IMP_OUT_OF_RANGE (IndexError), X and Y untouched, as
+ * imp_bpr_update.  IMP_INVALID_ARGUMENT: column counts differ or outside 2 .. 1024, a matrix not fp32, max_sampled outside
+ * 1 .. 4096, userids / itemids of different sizes, indptr not X.rows + 1 long.  nnz = 0 returns (0, 0) without a launch. */
+int imp_warp_update(const imp_intvector *userids, const imp_intvector *itemids, const imp_intvector *indptr, imp_matrix *X,
+                    imp_matrix *Y, float learning_rate, float regularization, int64_t seed, int max_sampled, int64_t samples,
+                    int64_t *satisfied, int64_t *trials);
+
 /* ---- LMF training (no reference GPU counterpart: implicit/lmf.py raises for use_gpu=True) --------------------------- */
 /* One Adagrad half-sweep of Logistic Matrix Factorization: X (rows of cui x C) is updated against the read-only Y (columns
  * of cui x C), deriv_sum_sq (shape of X) accumulates the squared gradients.  fp32, C = factors + 2 in 3 .. 1024.  The
