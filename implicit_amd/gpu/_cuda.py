@@ -8,8 +8,9 @@ released (ctypes.CDLL does that), as the reference does with `with nogil` (_cuda
 
 NEW relative to the reference: LeastSquaresSolver.least_squares_cholesky (the reference GPU path
 has no Cholesky solver), the Comm class (RCCL exchange for the multi-GPU fit), lmf_update (the
-reference has no GPU LMF), SpMat / sparse_topk_product (the reference's nearest-neighbour models are CPU only) and IVFIndex
-(a native IVF-Flat index in place of the faiss one the reference's ann wrappers build).
+reference has no GPU LMF), SpMat / sparse_topk_product (the reference's nearest-neighbour models are CPU only), IVFIndex
+(a native IVF-Flat index in place of the faiss one the reference's ann wrappers build) and ease_gram / spd_inverse /
+ease_weights / ease_topk (the EASE model, which the reference does not have).
 """
 import ctypes
 
@@ -542,6 +543,79 @@ def sparse_topk_product(A, B, k, zero_own_columns=False):
     counts = np.empty(rows, dtype=np.int32)
     check(lib().imp_sparse_topk_product(A._h, B._h, k, 1 if zero_own_columns else 0, _vp(ids), _vp(scores), _vp(counts)))
     return ids, scores, counts
+
+
+def ease_gram(item_users, user_items, regularization, G=None):
+    """NEW: G = X^T X + regularization I as a float32 items x items device Matrix (imp_ease_gram, ease.hip) from the two
+    orientations of X as CSRMatrix handles: item_users (items x users) and user_items (users x items, duplicates summed).
+    Every entry is the fp32 sum over the co-occurring users in item_users' stored order; G is exactly symmetric.  `G`: a
+    Matrix to write into (default: a new one).  Shapes that do not agree raise ValueError."""
+    if not isinstance(item_users, CSRMatrix) or not isinstance(user_items, CSRMatrix):
+        raise TypeError("ease_gram: item_users and user_items must be implicit_amd.gpu.CSRMatrix")
+    if G is None:
+        G = Matrix.zeros(item_users.shape[0], item_users.shape[0])
+    elif not isinstance(G, Matrix):
+        raise TypeError("ease_gram: G must be an implicit_amd.gpu.Matrix")
+    check(lib().imp_ease_gram(item_users._h, user_items._h, float(regularization), G._h))
+    return G
+
+
+def spd_inverse(A):
+    """NEW: replaces the symmetric positive definite float32 Matrix A by its inverse (imp_spd_inverse, spd_inverse.hip: a
+    blocked Cholesky inverse on the fp32 matrix cores).  Only the lower triangle is read; the result is exactly symmetric.
+    A pivot that is not positive raises ValueError with .failed_pivot = the smallest failing index (A is then unspecified);
+    a workspace that cannot be allocated raises RuntimeError naming the bytes."""
+    if not isinstance(A, Matrix):
+        raise TypeError("spd_inverse: A must be an implicit_amd.gpu.Matrix")
+    failed = ctypes.c_int64(-1)
+    try:
+        check(lib().imp_spd_inverse(A._h, ctypes.byref(failed)))
+    except ValueError as e:
+        e.failed_pivot = failed.value  # -1 unless the factorisation itself failed
+        raise
+    return A
+
+
+def ease_weights(P):
+    """NEW: in place B[i, j] = -(P[i, j] / P[j, j]), B[j, j] = 0 on a square float32 Matrix (imp_ease_weights): one IEEE
+    division and a sign flip per entry.  A zero or non-finite diagonal entry raises ValueError with P untouched."""
+    if not isinstance(P, Matrix):
+        raise TypeError("ease_weights: P must be an implicit_amd.gpu.Matrix")
+    check(lib().imp_ease_weights(P._h))
+    return P
+
+
+def ease_topk(knn, B, rows, k, filter_liked=False, item_filter=None):
+    """NEW: the k best columns of x B for every row x of the scipy CSR matrix `rows` (imp_ease_topk, ease.hip).  B: a float32
+    items x items Matrix; rows: one query per row, canonical (columns strictly increasing), values taken as float32.  A score
+    is the fp32 sum of the row's products x_i B[i, j] in stored order.  filter_liked: the row's own columns score -FLT_MAX
+    (they stay candidates); item_filter: an IntVector (or int32 array) of ids treated likewise.  Returns (ids int32, scores
+    float32), rows x k, best first under (score, id) descending, padded with (-1, -FLT_MAX) past min(k, items).  k outside
+    1 .. 1024, columns outside the model or not increasing raise ValueError."""
+    if not isinstance(knn, KnnQuery) or not isinstance(B, Matrix):
+        raise TypeError("ease_topk expects a KnnQuery and an implicit_amd.gpu.Matrix")
+    k = int(k)
+    n = int(rows.shape[0])
+    indptr = np.ascontiguousarray(rows.indptr, dtype=np.int64)
+    indices = np.asarray(rows.indices)
+    if indices.dtype != np.int32 and len(indices) and (indices.max() > np.iinfo(np.int32).max or indices.min() < 0):
+        raise ValueError("ease_topk: column index out of range")
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    data = np.ascontiguousarray(rows.data, dtype=np.float32)
+    if item_filter is not None and not isinstance(item_filter, IntVector):
+        item_filter = IntVector(np.ascontiguousarray(item_filter, dtype=np.int32))
+    ids = np.empty((n, max(k, 0)), dtype=np.int32)
+    scores = np.empty((n, max(k, 0)), dtype=np.float32)
+    check(lib().imp_ease_topk(knn._h, B._h, n, _vp(indptr), _vp(indices), _vp(data), k, 1 if filter_liked else 0,
+                              item_filter._h if item_filter is not None else None, _vp(ids), _vp(scores)))
+    return ids, scores
+
+
+def mem_get_info():
+    """(free, total) device memory in bytes (imp_mem_get_info)."""
+    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    check(lib().imp_mem_get_info(ctypes.byref(free), ctypes.byref(total)))
+    return free.value, total.value
 
 
 def _eval_pattern(test_user_items, k):

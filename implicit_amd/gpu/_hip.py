@@ -124,6 +124,11 @@ _SIGNATURES = {
     "imp_ivf_search": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                        ctypes.c_void_p],
     "imp_ivf_destroy": [ctypes.c_void_p],
+    "imp_ease_gram": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p],
+    "imp_spd_inverse": [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)],
+    "imp_ease_weights": [ctypes.c_void_p],
+    "imp_ease_topk": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     "imp_comm_unique_id": [ctypes.c_void_p],
     "imp_comm_init_rank": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_void_pp],
     "imp_comm_destroy": [ctypes.c_void_p],

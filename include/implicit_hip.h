@@ -366,6 +366,42 @@ int imp_ivf_lists(const imp_ivf *ix, float *centroids, int64_t *list_offsets, in
 int imp_ivf_search(imp_ivf *ix, const imp_matrix *query, int k, int nprobe, int32_t *indices, float *distances, int32_t *probes);
 int imp_ivf_destroy(imp_ivf *ix);
 
+/* ---- NEW: EASE, the closed-form item-item model B = I - P diag(P)^-1, P = (X^T X + reg I)^-1 (Steck 2019; no reference
+ * counterpart; csrc/ease.hip, csrc/spd_inverse.hip).  No floating-point atomics anywhere: equal inputs give
+ * bitwise equal outputs.  All four calls are synchronous. ---------------------------------------------------------------- */
+/* G (caller-allocated fp32, items x items) = X^T X + regularization I from BOTH orientations of the same matrix: item_users
+ * (items x users) and user_items (users x items, no column repeated within a row).  G[i][j], j <= i, is the fp32 sum of the
+ * separately rounded products x_ui x_uj over the co-occurring users u in item_users[i]'s stored order, the diagonal plus
+ * regularization last; j > i is a copy, so G is exactly symmetric.  Exact when the values are integers and every partial sum
+ * stays below 2^24; otherwise |G[i][j] - exact| <= (c_ij + 1) 2^-24 sum_u |x_ui x_uj| with c_ij co-occurring users.
+ * IMP_INVALID_ARGUMENT before any launch: shapes or nonzero counts that do not agree, more than 2^31 - 1 nonzeros, a G that
+ * is not fp32 items x items. */
+int imp_ease_gram(const imp_csr *item_users, const imp_csr *user_items, float regularization, imp_matrix *G);
+/* In-place inverse of a symmetric positive definite fp32 n x n matrix by a blocked Cholesky inverse on the fp32 matrix
+ * instruction.  Only the lower triangle of A is read; the full, exactly symmetric inverse is written.  On a pivot that is not
+ * positive (or NaN) returns IMP_INVALID_ARGUMENT with *failed_pivot = the smallest failing index (else -1), the rule of
+ * imp_solver_least_squares_cholesky; A is then unspecified.  Workspace: one more n x n fp32 matrix plus n nb floats (nb =
+ * 128, n rounded up to it); IMP_RUNTIME_ERROR with a message naming the bytes when it cannot be allocated.  IMP_INVALID_ARGUMENT before any
+ * launch: a matrix that is not square fp32. */
+int imp_spd_inverse(imp_matrix *A, int64_t *failed_pivot);
+/* In place on a square fp32 matrix: B[i][j] = -(P[i][j] / P[j][j]) for i != j, one IEEE fp32 division and a sign flip;
+ * B[j][j] = 0.  IMP_INVALID_ARGUMENT with P untouched: a diagonal entry that is zero or not finite, a matrix that is not
+ * square fp32. */
+int imp_ease_weights(imp_matrix *P);
+/* The topk best columns of x B for every row x of a HOST CSR matrix (rows + 1 int64 offsets from 0, int32 columns strictly
+ * increasing inside a row and inside [0, items), fp32 values); B: fp32 items x items on the device.  The score of column j
+ * for a row with stored entries (i_1, x_1), (i_2, x_2), ... is ((0 + x_1 B[i_1][j]) + x_2 B[i_2][j]) + ..., every product and
+ * sum a separately rounded fp32 operation in stored order; an empty row scores 0 everywhere.  filter_liked: the row's own
+ * columns score -FLT_MAX and stay candidates (the rule of imp_knn_topk); the ids of item_filter (nullable) likewise.  HOST
+ * outputs ids / scores[rows x topk], best first in the total order (score desc, id desc, -0.0 as +0.0); the tail past
+ * min(topk, items) is id -1, score -FLT_MAX.  Rows are processed in chunks that fit the handle's max_temp_memory; the
+ * chunking changes no result.  IMP_INVALID_ARGUMENT before any launch, nothing written: topk outside 1 .. 1024, a B that is
+ * not square fp32, negative rows, offsets that do not start at 0 or that decrease, a column outside the model, a row not
+ * strictly increasing, an item_filter id outside the model, a single row whose temporaries exceed max_temp_memory. */
+int imp_ease_topk(imp_knn *k, const imp_matrix *B, int32_t rows, const int64_t *indptr, const int32_t *indices,
+                  const float *data, int topk, int filter_liked, const imp_intvector *item_filter, int32_t *ids,
+                  float *scores);
+
 /* ---- NEW: multi-GPU exchange over RCCL / xGMI (no reference counterpart) ------------------------ */
 /* One process per GPU.  Rank 0 calls imp_comm_unique_id, the host side broadcasts the 128 bytes by
  * any means (torch.distributed store, MPI, a file) and every rank calls imp_comm_init_rank. */
