@@ -83,7 +83,10 @@ def test_host_metrics_equal_the_reference(golden, host, K):
     np.testing.assert_allclose(per_row[:, 1:], ref_rows[:, 1:], rtol=RTOL, atol=0)
 
 
-@pytest.mark.parametrize("K,wide", [(1, False), (7, True), (64, False), (65, True), (130, False)])
+@pytest.mark.parametrize("K,wide", [(1, False), (7, True), (64, False), (65, True), (130, False),
+                                    # the K the device tests compare the kernel with this function at (tests/test_gpu_eval.py)
+                                    (2, False), (5, True), (8, False), (17, True), (32, False), (128, True), (129, False),
+                                    (200, True)])
 def test_host_metrics_equal_numpy_on_random_input(host, K, wide):
     rng = np.random.default_rng(100 + K)
     users, items, n = 300, 211, 700

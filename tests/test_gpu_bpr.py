@@ -9,6 +9,7 @@ from numpy.testing import assert_array_equal
 from scipy.sparse import csr_matrix
 
 import bpr_reference as ref
+import sgd_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -55,10 +56,21 @@ def _check_against(Xg, Yg, X64, Y64, X0, Y0, users, items):
     assert (Xg[:, -1] == 1.0).all()
 
 
+def _check_call(Xg, Yg, X64, Y64, X0, Y0, users, items):
+    """_check_against for large matrices: the untouched rows are compared in one piece."""
+    for u in users:
+        assert _rel(Xg[u], X64[u]) < 2e-6, ("user", u)
+    for i in items:
+        assert _rel(Yg[i], Y64[i]) < 2e-6, ("item", i)
+    untouched_u = np.array(sorted(set(range(X0.shape[0])) - set(users)))
+    untouched_i = np.array(sorted(set(range(Y0.shape[0])) - set(items)))
+    assert_array_equal(Xg[untouched_u].view(np.uint32), X0[untouched_u].view(np.uint32))
+    assert_array_equal(Yg[untouched_i].view(np.uint32), Y0[untouched_i].view(np.uint32))
+    assert (Xg[:, -1] == 1.0).all()
+
+
 # ---- 1. single samples are exact ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("verify", [False, True])
-@pytest.mark.parametrize("C", [2, 17, 33, 65, 101, 129, 257, 1024])
-def test_single_steps_exact(gpu, C, verify):
+def _single_steps_exact(gpu, C, verify):
     m = _small_matrix()
     rng = np.random.default_rng(C * 2 + verify)
     X0, Y0 = _factors(m.shape[0], C, rng, bias=1.0), _factors(m.shape[1], C, rng)
@@ -92,6 +104,22 @@ def test_single_steps_exact(gpu, C, verify):
         Xc, Yc = Xg, Yg
 
 
+@pytest.mark.parametrize("verify", [False, True])
+@pytest.mark.parametrize("C", sc.DISPATCH_C)  # both ends of every (lanes, columns per lane) instantiation
+def test_single_steps_exact(gpu, C, verify):
+    _single_steps_exact(gpu, C, verify)
+
+
+@pytest.mark.parametrize("lanes, C", [(lanes, C) for lanes, C, _ in sc.LANE_OVERRIDES])
+def test_lane_override_routes(gpu, monkeypatch, lanes, C):
+    """IMP_BPR_LANES is read by every call (bpr_group): other group widths than the dispatch picks reach the twelve
+    instantiations nothing else does (sgd_cases.LANE_OVERRIDES).  16 lanes at C = 257 cannot hold a row in 16 registers a
+    lane: there the switch is ignored."""
+    monkeypatch.setenv("IMP_BPR_LANES", str(lanes))
+    _single_steps_exact(gpu, C, True)
+    _single_steps_exact(gpu, C, False)
+
+
 # ---- 2. a multi-sample call without conflicts is exact --------------------------------------------------------------------
 @pytest.mark.parametrize("C", [17, 101, 257, 1024])
 def test_conflict_free_call_exact(gpu, C):
@@ -121,6 +149,24 @@ def test_conflict_free_call_exact(gpu, C):
     assert_array_equal(Xg[untouched_u], X0[untouched_u])
     assert_array_equal(Yg[untouched_i], Y0[untouched_i])
     assert (Xg[:, -1] == 1.0).all()
+
+
+@pytest.mark.parametrize("C", sc.ROUNDS_C)
+def test_conflict_free_call_exact_over_rounds(gpu, C):
+    """24 samples on a 256-user matrix: 16 samples in flight, so every group's loop takes a second step for half of the
+    groups, with the second sample's draw prefetched during the first (sgd_cases.py, section 2)."""
+    m = sc.rounds_matrix()
+    n = sc.ROUNDS_N
+    seed, u, i, j = sc.bpr_rounds_seed(m)
+    X0, Y0 = sc.rounds_factors(m, C)
+    X64, Y64 = X0.astype(np.float64), Y0.astype(np.float64)
+    correct = sum(ref.step64(X64, Y64, a, b, c, LR, REG) > 0 for a, b, c in zip(u.tolist(), i.tolist(), j.tolist()))
+    uid, iid, ptr = _device_ids(gpu, m)
+    X, Y = gpu.Matrix(X0), gpu.Matrix(Y0)
+    got = gpu.bpr_epoch(uid, iid, ptr, X, Y, LR, REG, seed, False, samples=n)
+    assert got == (correct, 0)
+    Xg, Yg = X.to_numpy(), Y.to_numpy()
+    _check_call(Xg, Yg, X64, Y64, X0, Y0, set(u.tolist()), set(i.tolist()) | set(j.tolist()))
 
 
 # ---- 3. whole epochs ------------------------------------------------------------------------------------------------------
@@ -153,6 +199,27 @@ def test_whole_epoch(gpu, name, C):
         assert (Xg[:, -1] == 1.0).all()
         assert not np.array_equal(Yg, Y0)
     assert want == 0
+
+
+@pytest.mark.parametrize("C", sc.SEARCH_C)
+def test_zero_learning_rate_epoch_is_exact(gpu, C):
+    """lr = reg = 0: every store writes back what its lane loaded, so an epoch -- some 22 000 chained samples, 16 in flight --
+    returns counts that are a pure function of the initial factors, and X and Y bit for bit.  The matrix has rows on both
+    sides of every cut of the membership search (sgd_cases.search_matrix; tests/test_sgd_cases_host.py shows which hits and
+    misses the epoch meets).  `correct` is compared with samples of a float64 |score| < 1e-6 left out: none at these C."""
+    m = sc.search_matrix()
+    X0, Y0 = sc.bpr_frozen_factors(m, C)
+    skipped, correct_lo, unsure, _, _ = sc.bpr_frozen_counts(m, X0, Y0)
+    assert skipped == ref.predicted_skipped(m, sc.SEARCH_EPOCH_SEED, True) and unsure <= 0.001 * m.nnz
+    uid, iid, ptr = _device_ids(gpu, m)
+    X, Y = gpu.Matrix(X0), gpu.Matrix(Y0)
+    for _ in range(2):
+        correct, got_skipped = gpu.bpr_epoch(uid, iid, ptr, X, Y, 0.0, 0.0, sc.SEARCH_EPOCH_SEED, True)
+        print(f"C={C}: correct {correct} (float64 {correct_lo} .. {correct_lo + unsure}), skipped {got_skipped} ({skipped})")
+        assert got_skipped == skipped
+        assert correct_lo <= correct <= correct_lo + unsure
+        assert_array_equal(X.to_numpy().view(np.uint32), X0.view(np.uint32))
+        assert_array_equal(Y.to_numpy().view(np.uint32), Y0.view(np.uint32))
 
 
 # ---- 4. learning quality --------------------------------------------------------------------------------------------------
@@ -347,6 +414,33 @@ def test_argument_errors(gpu):
     bad_u[0] = -1
     with pytest.raises(IndexError):
         gpu.bpr_epoch(gpu.IntVector(bad_u), iid, ptr, X, Y, LR, REG, 1, False)
+    # the pre-pass reads the ids four at a time and the rest one by one: a bad id in the last position of every tail length,
+    # and row pointers outside [0, nnz]
+    users_all, items_all = ref.coo_ids(m)
+    for tail in (1, 2, 3):
+        nnz = (m.nnz - 4) // 4 * 4 + tail
+        mt = csr_matrix((m.data[:nnz], m.indices[:nnz], np.minimum(m.indptr, nnz)), shape=m.shape)
+        assert mt.nnz == nnz and nnz % 4 == tail
+        uid_t, iid_t, ptr_t = _device_ids(gpu, mt)
+        for bad_value in (m.shape[1], -1):
+            bad = items_all[:nnz].copy()
+            bad[-1] = bad_value
+            with pytest.raises(IndexError):
+                gpu.bpr_epoch(uid_t, gpu.IntVector(bad), ptr_t, X, Y, LR, REG, 1, False)
+        for bad_value in (m.shape[0], -1):
+            bad_u = users_all[:nnz].copy()
+            bad_u[-1] = bad_value
+            with pytest.raises(IndexError):
+                gpu.bpr_epoch(gpu.IntVector(bad_u), iid_t, ptr_t, X, Y, LR, REG, 1, False)
+        for at, bad_value in ((0, -1), (len(mt.indptr) // 2, -1), (len(mt.indptr) - 1, nnz + 1), (5, nnz + 1)):
+            bad_ptr = np.asarray(mt.indptr, dtype=np.int32).copy()
+            bad_ptr[at] = bad_value
+            with pytest.raises(IndexError):
+                gpu.bpr_epoch(uid_t, iid_t, gpu.IntVector(bad_ptr), X, Y, LR, REG, 1, True)
+        assert_array_equal(X.to_numpy().view(np.uint32), X0.view(np.uint32))
+        assert_array_equal(Y.to_numpy().view(np.uint32), Y0.view(np.uint32))
+        # a valid call still works
+        assert gpu.bpr_epoch(uid_t, iid_t, ptr_t, X, Y, 0.0, 0.0, 1, True)[1] == ref.predicted_skipped(mt, 1, True) > 0
     assert_array_equal(X.to_numpy(), X0)
     assert_array_equal(Y.to_numpy(), Y0)
     assert gpu.bpr_epoch(gpu.IntVector(np.zeros(0, np.int32)), gpu.IntVector(np.zeros(0, np.int32)),

@@ -14,6 +14,7 @@ from numpy.testing import assert_array_equal
 from scipy.sparse import coo_matrix, csr_matrix
 
 import lmf_reference as ref
+import sgd_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -75,13 +76,22 @@ def test_neg_prop_0_matches_reference(gpu, name):
 
 
 # ---- 2. neg_prop > 0 against the float64 restatement with the same draws ----------------------------------------------------
-@pytest.mark.parametrize("C", [3, 5, 32, 34, 66, 130, 1024])
+@pytest.mark.parametrize("C", sc.LMF_DISPATCH_C)  # both ends of every (lanes, columns per lane) instantiation of launch_lmf
 def test_half_sweeps_match_float64(gpu, C):
-    m = _class_matrix(24000 if C <= 130 else 3000, seed=C)
+    """The C the test ran at before keep the full class matrix; the ends of the dispatch ranges added to them run on the
+    reduced one (sgd_cases.lmf_reduced_matrix), whose float64 restatement stays below 100 MB an array at every C."""
+    if C in sc.LMF_EXISTING_C:
+        m = _class_matrix(24000 if C <= 130 else 3000, seed=C)
+    else:
+        m = sc.lmf_reduced_matrix(C, seed=C)
     mt = m.T.tocsr()
     mt.sort_indices()
     lens = np.diff(mt.indptr)
-    assert lens.max() > 2000 and (lens == 0).any() and ((lens > 16) & (lens <= 32)).any()
+    if C in sc.LMF_EXISTING_C:
+        assert lens.max() > 2000 and (lens == 0).any() and ((lens > 16) & (lens <= 32)).any()
+    else:
+        G = sc.lmf_instantiation(C)[0]
+        assert lens.max() > 512 and {512, G - 1, G, G + 1, 1, 0} <= set(lens.tolist())
     rng = np.random.default_rng(C)
     U, V = _factors(m.shape[0], C, rng), _factors(m.shape[1], C, rng)
     for name, csr, X0, Y0, neg_prop in (("items", mt, V, U, 30), ("users", m, U, V, 3)):
@@ -95,6 +105,35 @@ def test_half_sweeps_match_float64(gpu, C):
         assert empty.any()
         assert_array_equal(Xg[empty], X0[empty])
         assert_array_equal(Gg[empty], G0[empty])
+
+
+@pytest.mark.parametrize("rows, C, entries", sc.LMF_ROUND_SHAPES)
+def test_rows_kernel_second_grid_round(gpu, rows, C, entries):
+    """More rows of 1 .. 512 entries than lmf_rows_kernel has groups in flight on 256 CUs (32 768 at 16 lanes, 16 384 at 32,
+    8 192 at 64): its `i += ngroups` takes a second step.  The rows a dropped second step would leave alone are the last of
+    the schedule order, the shortest rows with the highest ids.  The 32-lane shape is the user side of the class matrix that
+    test_half_sweeps_match_float64 runs at C = 130; the other two have 40 items, so Y is small."""
+    m = _class_matrix(rows, seed=C) if C == 130 else sc.lmf_round_matrix(rows, entries, seed=C)
+    order = sc.lmf_schedule_order(m)
+    in_flight = sc.lmf_groups_in_flight(C)
+    assert m.shape[0] == rows and in_flight < len(order) < 2 * in_flight
+    rng = np.random.default_rng(C)
+    X0, Y0 = _factors(m.shape[0], C, rng), _factors(m.shape[1], C, rng)
+    G0 = rng.uniform(0.0, 2.0, X0.shape).astype(np.float32)
+    Xg, Gg = _sweep(gpu, m, X0, Y0, G0, 0.7, 0.2, 1, 99)
+    X64, G64, bX, bG = ref.half_sweep64(m, X0, Y0, G0, 0.7, 0.2, 1, 99)
+    second = order[in_flight:]  # the rows of the second step
+    _assert_within(Xg[second], X64[second], bX[second], "X, rows of the second round")
+    _assert_within(Gg[second], G64[second], bG[second], "G, rows of the second round")
+    _assert_within(Xg, X64, bX, "X")
+    _assert_within(Gg, G64, bG, "G")
+    empty = np.diff(m.indptr) == 0
+    assert empty.any()
+    assert_array_equal(Xg[empty], X0[empty])
+    assert_array_equal(Gg[empty], G0[empty])
+    # no row with entries is left as it was: the bound alone would let a row through whose step is below it
+    assert not (Xg[~empty] == X0[~empty]).all(axis=1).any()
+    assert not (Gg[~empty] == G0[~empty]).all(axis=1).any()
 
 
 # ---- 3. the negative count -------------------------------------------------------------------------------------------------

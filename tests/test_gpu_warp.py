@@ -10,8 +10,9 @@ from numpy.testing import assert_array_equal
 from scipy.sparse import csr_matrix
 
 import bpr_reference as bref
+import sgd_cases as sc
 import warp_reference as ref
-from test_gpu_bpr import _check_against, _device_ids, _factors, _held_out_auc, _knn_ids, _planted, _rel, _small_matrix
+from test_gpu_bpr import _check_against, _check_call, _device_ids, _factors, _held_out_auc, _knn_ids, _planted, _rel, _small_matrix
 
 pytestmark = pytest.mark.gpu
 
@@ -20,8 +21,7 @@ MARGIN = 1e-4  # seeds are chosen so that no examined trial is closer to the vio
 
 
 # ---- 1. single samples are exact ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", [2, 17, 33, 65, 101, 129, 257, 1024])
-def test_single_steps_exact(gpu, C):
+def _single_steps_exact(gpu, C):
     """25 chained single-sample calls, max_sampled 6 (the second Philox block is used).  The seeds are picked on the host, from
     2000 at most, for a closest margin >= 1e-4 on the factors the chain has reached; at least 3 have a liked first candidate
     and at least 3 a first violation at t >= 2."""
@@ -59,7 +59,21 @@ def test_single_steps_exact(gpu, C):
     assert liked_first >= 3 and late >= 3, (liked_first, late)
 
 
-@pytest.mark.parametrize("C", [2, 17, 33, 65, 101, 129, 257, 1024])
+@pytest.mark.parametrize("C", sc.DISPATCH_C)  # both ends of every (lanes, columns per lane) instantiation
+def test_single_steps_exact(gpu, C):
+    _single_steps_exact(gpu, C)
+
+
+@pytest.mark.parametrize("lanes, C", [(lanes, C) for lanes, C, _ in sc.LANE_OVERRIDES])
+def test_lane_override_routes(gpu, monkeypatch, lanes, C):
+    """IMP_BPR_LANES is read by every call (bpr_group): other group widths than the dispatch picks reach the twelve
+    instantiations nothing else does (sgd_cases.LANE_OVERRIDES).  16 lanes at C = 257 cannot hold a row in 16 registers a
+    lane: there the switch is ignored."""
+    monkeypatch.setenv("IMP_BPR_LANES", str(lanes))
+    _single_steps_exact(gpu, C)
+
+
+@pytest.mark.parametrize("C", sc.DISPATCH_C)
 def test_satisfied_sample_writes_nothing(gpu, C):
     """|dot| < 1 without the bias; the bias is -4 on every item outside the user's row and 0 inside it: no candidate violates."""
     m = _small_matrix()
@@ -129,6 +143,32 @@ def test_conflict_free_call_exact(gpu, C, sparse_matrix):
     assert (Xg[:, -1] == 1.0).all()
 
 
+@pytest.fixture(scope="module")
+def rounds_matrix():
+    m = sc.rounds_matrix()
+    return m, ref.liked_sets(m)
+
+
+@pytest.mark.parametrize("C", sc.ROUNDS_C)
+def test_conflict_free_call_exact_over_rounds(gpu, C, rounds_matrix):
+    """24 samples on a 256-user matrix: 16 samples in flight, so half of the groups start a second sample, in the pass where
+    their neighbours run their next trial or have left the loop (sgd_cases.py, section 2).  The margin filter and the seed
+    search are those of test_conflict_free_call_exact."""
+    m, rows = rounds_matrix
+    n = sc.ROUNDS_N
+    case = sc.warp_rounds_case(m, rows, C)
+    assert case is not None, "no conflict-free seed found"
+    us, touched, X0, Y0, X64, Y64 = (case[k] for k in ("us", "touched", "X0", "Y0", "X64", "Y64"))
+    assert case["satisfied"] < n  # the call does update
+    uid, iid, ptr = _device_ids(gpu, m)
+    X, Y = gpu.Matrix(X0), gpu.Matrix(Y0)
+    got = gpu.warp_epoch(uid, iid, ptr, X, Y, LR, REG, case["seed"], sc.ROUNDS_MAX_SAMPLED, samples=n)
+    assert got == (case["satisfied"], case["trials"])
+    Xg, Yg = X.to_numpy(), Y.to_numpy()
+    # a satisfied sample's user and positive are listed as touched and unchanged in float64: 0 relative difference
+    _check_call(Xg, Yg, X64, Y64, X0, Y0, set(us), set(touched))
+
+
 # ---- 3. a whole epoch -----------------------------------------------------------------------------------------------------
 def test_whole_epoch(gpu):
     from implicit_amd.synthetic import named
@@ -151,6 +191,27 @@ def test_whole_epoch(gpu):
     assert_array_equal(Xg[empty_users], X0[empty_users])
     assert (Xg[:, -1] == 1.0).all()
     assert not np.array_equal(Yg, Y0)  # never-liked items may change too: they are valid negatives here
+
+
+@pytest.mark.parametrize("C", sc.SEARCH_C)
+def test_zero_learning_rate_epoch_is_exact(gpu, C):
+    """lr = reg = 0: every store writes back what its lane loaded, so an epoch -- some 22 000 chained samples, 16 in flight,
+    63 000 trials -- returns the counts of the serial restatement on the initial factors, and X and Y bit for bit.  The matrix
+    has rows on both sides of every cut of the membership search, six items in seven carry a bias of -4 so that satisfied,
+    first-trial and late samples all occur, and no margin of the epoch is below 1e-4 (sgd_cases.py, section 3;
+    tests/test_sgd_cases_host.py shows which hits and misses the epoch meets)."""
+    m = sc.search_matrix()
+    X0, Y0 = sc.warp_frozen_factors(m, C)
+    _, _, (want,), closest = ref.serial_epochs(m, X0, Y0, [sc.SEARCH_EPOCH_SEED], 0.0, 0.0, sc.SEARCH_MAX_SAMPLED, with_margin=True)
+    assert closest >= MARGIN and 0 < want[0] < m.nnz
+    uid, iid, ptr = _device_ids(gpu, m)
+    X, Y = gpu.Matrix(X0), gpu.Matrix(Y0)
+    for _ in range(2):
+        got = gpu.warp_epoch(uid, iid, ptr, X, Y, 0.0, 0.0, sc.SEARCH_EPOCH_SEED, sc.SEARCH_MAX_SAMPLED)
+        print(f"C={C}: (satisfied, trials) {got}, serial {want}, closest margin {closest:.3g}")
+        assert got == want
+        assert_array_equal(X.to_numpy().view(np.uint32), X0.view(np.uint32))
+        assert_array_equal(Y.to_numpy().view(np.uint32), Y0.view(np.uint32))
 
 
 # ---- 4. learning quality --------------------------------------------------------------------------------------------------
@@ -334,6 +395,35 @@ def test_argument_errors(gpu):
     bad_u[0] = -1
     with pytest.raises(IndexError):
         gpu.warp_epoch(gpu.IntVector(bad_u), iid, ptr, X, Y, LR, REG, 1)
+    # the pre-pass reads the ids four at a time and the rest one by one: a bad id in the last position of every tail length,
+    # and row pointers outside [0, nnz]
+    users_all, items_all = bref.coo_ids(m)
+    for tail in (1, 2, 3):
+        nnz = (m.nnz - 4) // 4 * 4 + tail
+        mt = csr_matrix((m.data[:nnz], m.indices[:nnz], np.minimum(m.indptr, nnz)), shape=m.shape)
+        assert mt.nnz == nnz and nnz % 4 == tail
+        uid_t, iid_t, ptr_t = _device_ids(gpu, mt)
+        for bad_value in (m.shape[1], -1):
+            bad = items_all[:nnz].copy()
+            bad[-1] = bad_value
+            with pytest.raises(IndexError):
+                gpu.warp_epoch(uid_t, gpu.IntVector(bad), ptr_t, X, Y, LR, REG, 1)
+        for bad_value in (m.shape[0], -1):
+            bad_u = users_all[:nnz].copy()
+            bad_u[-1] = bad_value
+            with pytest.raises(IndexError):
+                gpu.warp_epoch(gpu.IntVector(bad_u), iid_t, ptr_t, X, Y, LR, REG, 1)
+        for at, bad_value in ((0, -1), (len(mt.indptr) // 2, -1), (len(mt.indptr) - 1, nnz + 1), (5, nnz + 1)):
+            bad_ptr = np.asarray(mt.indptr, dtype=np.int32).copy()
+            bad_ptr[at] = bad_value
+            with pytest.raises(IndexError):
+                gpu.warp_epoch(uid_t, iid_t, gpu.IntVector(bad_ptr), X, Y, LR, REG, 1)
+        assert_array_equal(X.to_numpy().view(np.uint32), X0.view(np.uint32))
+        assert_array_equal(Y.to_numpy().view(np.uint32), Y0.view(np.uint32))
+        # a valid call still works: at a zero learning rate its counts are the serial restatement's
+        _, _, (want,), closest = ref.serial_epochs(mt, X0, Y0, [1], 0.0, 0.0, 3, with_margin=True)
+        assert closest >= MARGIN
+        assert gpu.warp_epoch(uid_t, iid_t, ptr_t, X, Y, 0.0, 0.0, 1, 3) == want
     assert_array_equal(X.to_numpy(), X0)
     assert_array_equal(Y.to_numpy(), Y0)
     assert gpu.warp_epoch(gpu.IntVector(np.zeros(0, np.int32)), gpu.IntVector(np.zeros(0, np.int32)),

@@ -1,7 +1,7 @@
 """Host restatements of the WARP contract (csrc/warp.hip), written from its equations, for the WARP tests.
 
 positives: the (u, i) of a call's samples.  candidates: the items a sample draws, in trial order.  weight: the rank
-estimate's weight L.  step64: one sample in float64.  serial_epochs: the whole serial SGD over the device's draws.
+estimate's weight L.  step64: one sample in float64.  serial_epochs: the whole serial SGD over the device's draws (and its closest margin).
 """
 import math
 
@@ -72,12 +72,13 @@ def liked_sets(m):
     return [set(m.indices[m.indptr[u]:m.indptr[u + 1]].tolist()) for u in range(m.shape[0])]
 
 
-def serial_epochs(m, X0, Y0, seeds, lr, reg, max_sampled):
-    """The serial SGD over the device's draws, float64; returns X, Y and the per-epoch (satisfied, trials)."""
+def serial_epochs(m, X0, Y0, seeds, lr, reg, max_sampled, with_margin=False):
+    """The serial SGD over the device's draws, float64; returns X, Y and the per-epoch (satisfied, trials), and with
+    `with_margin` also the closest margin |sn - sp + 1| over every examined trial of every epoch."""
     X, Y = X0.astype(np.float64), Y0.astype(np.float64)
     rows = liked_sets(m)
     items = m.shape[1]
-    counts = []
+    counts, closest = [], math.inf
     blocks = (max_sampled + 3) // 4
     for seed in seeds:
         us, iis = positives(m, seed)
@@ -87,8 +88,9 @@ def serial_epochs(m, X0, Y0, seeds, lr, reg, max_sampled):
         cands = ((words[:, :max_sampled].astype(np.uint64) * np.uint64(items)) >> np.uint64(32)).astype(np.int64)
         satisfied = trials = 0
         for k, (u, i) in enumerate(zip(us.tolist(), iis.tolist())):
-            t, used, _ = step64(X, Y, rows[u], u, i, cands[k], lr, reg)
+            t, used, margin = step64(X, Y, rows[u], u, i, cands[k], lr, reg)
             satisfied += t is None
             trials += used
+            closest = min(closest, margin)
         counts.append((satisfied, trials))
-    return X, Y, counts
+    return (X, Y, counts, closest) if with_margin else (X, Y, counts)
