@@ -217,7 +217,7 @@ struct Context {
   DeviceArray<unsigned> wide_counters;           // the same for the chained 1024-thread classes (launch_wide_chain)
   WideTickets wide_tickets;
   DeviceArray<int> nm_ticket;                    // work counter of the normal-matrix kernel (als_cg_nm.hip), reset by every launch
-  DeviceArray<unsigned long long> pair_stats;    // [0], [1]: the two counts of a pairwise SGD call (bpr_update: correct / skipped; warp_update: satisfied / trials), [2]: the id check's violation bits (pair_sgd.h)
+  DeviceArray<unsigned long long> pair_stats;    // [0], [1]: the two counts of a pairwise SGD call (bpr_update: correct / skipped; warp_update: satisfied / trials), [2]: the id check's violation bits (pair_sgd.hip)
   DeviceArray<float> lmf_ws;                     // partial sums of the long rows' segments of lmf_update (lmf.hip)
   DeviceArray<double> knn_acc;                   // dense per-worker accumulators of sparse_topk_product, kept at a sentinel (knn.hip)
   DeviceArray<int32_t> knn_touched;              // the workers' touched-column lists (knn.hip)

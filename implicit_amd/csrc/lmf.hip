@@ -19,13 +19,13 @@
 // key (seed_lo, seed_hi) (philox.h).  The negatives, and so the result, are a pure function of (seed, CSR, X, Y); there
 // are no float atomics and every sum runs in a fixed order, so two identical calls give bitwise identical X and G.
 //
-// Layout.  One GROUP of G = 16 / 32 / 64 lanes per row (bpr.hip's choice: a row in at most 16 registers per lane); lane l
+// Layout (sgd_group.h, shared with bpr.hip and warp.hip).  One GROUP of G = 16 / 32 / 64 lanes per row (group_lanes); lane l
 // owns columns l, l + G, ... of X[u], the gathered Y rows and the accumulator d.  Row stride is C x 4 bytes (4-byte aligned
 // only in general: C = 5, 34, 102), so the loads are dwords, coalesced across the group.  The row's entries -- positives,
 // then negatives -- are taken G at a time: lane l first resolves entry l of the chunk to a Y row (indices[p] for a
 // positive; the Philox draw and indices[pos] for a negative), all lanes at once; then the group gathers B rows at a time
 // (B = 8 / 4 / 2 by row width), so B row loads per group are in flight before the first dot product (a DPP butterfly,
-// wave_ops.h group_allsum) waits.
+// group_dot) waits.
 //
 // Row classes (imp_csr): rows of classes 1..6 (1..512 nonzeros) go one group per row, longest first (lmf_rows_kernel).  The
 // long rows of class 0 are cut by the CSR's plan_all into segments of <= 512 nonzeros; lmf_segment_kernel writes each
@@ -35,7 +35,7 @@
 
 #include "common.h"
 #include "philox.h"
-#include "wave_ops.h"
+#include "sgd_group.h"
 
 namespace imp {
 
@@ -111,10 +111,7 @@ __device__ __forceinline__ void lmf_accumulate(const LmfArgs &a, int row, const 
       }
 #pragma unroll
       for (int b = 0; b < B; ++b) {
-        float part = 0.f;
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) part = fmaf(x[k], y[b][k], part);
-        const float s = group_allsum<G>(part);  // bitwise the same in every lane of the group
+        const float s = group_dot<G>(x, y[b]);  // bitwise the same in every lane of the group
         const float coef = kb[b] == 1 ? wb[b] * lmf_sigmoid(-s) : kb[b] == 2 ? -lmf_sigmoid(s) : 0.f;
 #pragma unroll
         for (int k = 0; k < CPL; ++k) acc[k] = fmaf(coef, y[b][k], acc[k]);
@@ -123,21 +120,17 @@ __device__ __forceinline__ void lmf_accumulate(const LmfArgs &a, int row, const 
   }
 }
 
+// x = row `row` of X, acc = 0
 template <int G, int CPL>
-__device__ __forceinline__ void lmf_load_row(const LmfArgs &a, int row, float (&x)[CPL]) {
-  const int gl = threadIdx.x & (G - 1);
-  const float *xr = a.X + (size_t)row * a.C;
+__device__ __forceinline__ void lmf_begin_row(const LmfArgs &a, int gl, int row, float (&x)[CPL], float (&acc)[CPL]) {
+  group_load<G>(a.X + (size_t)row * a.C, a.C, gl, x);
 #pragma unroll
-  for (int k = 0; k < CPL; ++k) {
-    const int c = gl + G * k;
-    x[k] = c < a.C ? xr[c] : 0.f;
-  }
+  for (int k = 0; k < CPL; ++k) acc[k] = 0.f;
 }
 
 // d = acc - reg x;  G += d*d;  X += lr / sqrt(1e-6 + G) * d
 template <int G, int CPL>
-__device__ __forceinline__ void lmf_adagrad(const LmfArgs &a, int row, const float (&x)[CPL], const float (&acc)[CPL]) {
-  const int gl = threadIdx.x & (G - 1);
+__device__ __forceinline__ void lmf_adagrad(const LmfArgs &a, int gl, int row, const float (&x)[CPL], const float (&acc)[CPL]) {
   float *xr = a.X + (size_t)row * a.C, *gr = a.G + (size_t)row * a.C;
 #pragma unroll
   for (int k = 0; k < CPL; ++k) {
@@ -156,52 +149,42 @@ template <int CPL> constexpr int lmf_batch() { return CPL <= 2 ? 8 : CPL <= 4 ? 
 // rows of 1 .. 512 nonzeros: order[row_begin .. row_end), one group per row
 template <int G, int CPL>
 __global__ __launch_bounds__(256) void lmf_rows_kernel(LmfArgs a) {
-  const int64_t ngroups = (int64_t)gridDim.x * (blockDim.x / G);
-  for (int64_t i = a.row_begin + ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G; i < a.row_end; i += ngroups) {
+  const LaneGroup<G> g;
+  for (int64_t i = a.row_begin + g.index; i < a.row_end; i += g.ngroups) {
     const int row = a.order[i];
     const int64_t beg = a.indptr[row];
     const int n = a.indptr[row + 1] - (int32_t)beg;
     float x[CPL], acc[CPL];
-    lmf_load_row<G, CPL>(a, row, x);
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) acc[k] = 0.f;
+    lmf_begin_row<G>(a, g.gl, row, x, acc);
     lmf_accumulate<G, CPL, lmf_batch<CPL>()>(a, row, x, acc, beg, n, lmf_negatives(a, n));
-    lmf_adagrad<G, CPL>(a, row, x, acc);
+    lmf_adagrad<G>(a, g.gl, row, x, acc);
   }
 }
 
 // segments of the long rows: the positive terms of seg_begin .. seg_end, to ws[s * C ..]
 template <int G, int CPL>
 __global__ __launch_bounds__(256) void lmf_segment_kernel(LmfArgs a) {
-  const int gl = threadIdx.x & (G - 1);
-  const int64_t ngroups = (int64_t)gridDim.x * (blockDim.x / G);
-  for (int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G; s < a.plan.n_seg; s += ngroups) {
+  const LaneGroup<G> g;
+  for (int64_t s = g.index; s < a.plan.n_seg; s += g.ngroups) {
     const int row = a.plan.rows[a.plan.seg_row[s]];
     const int beg = a.plan.seg_begin[s];
     float x[CPL], acc[CPL];
-    lmf_load_row<G, CPL>(a, row, x);
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) acc[k] = 0.f;
+    lmf_begin_row<G>(a, g.gl, row, x, acc);
     lmf_accumulate<G, CPL, lmf_batch<CPL>()>(a, row, x, acc, beg, a.plan.seg_end[s] - beg, 0);
-    float *out = a.ws + (size_t)s * a.C;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k)
-      if (gl + G * k < a.C) out[gl + G * k] = acc[k];
+    group_store<G>(a.ws + (size_t)s * a.C, a.C, g.gl, acc);
   }
 }
 
 // long rows: negatives, then the segments' partials in segment order, then Adagrad
 template <int G, int CPL>
 __global__ __launch_bounds__(256) void lmf_finish_kernel(LmfArgs a) {
-  const int gl = threadIdx.x & (G - 1);
-  const int64_t ngroups = (int64_t)gridDim.x * (blockDim.x / G);
-  for (int64_t li = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G; li < a.plan.n_long; li += ngroups) {
+  const LaneGroup<G> g;
+  const int gl = g.gl;
+  for (int64_t li = g.index; li < a.plan.n_long; li += g.ngroups) {
     const int row = a.plan.rows[li];
     const int n = a.indptr[row + 1] - a.indptr[row];
     float x[CPL], acc[CPL];
-    lmf_load_row<G, CPL>(a, row, x);
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) acc[k] = 0.f;
+    lmf_begin_row<G>(a, gl, row, x, acc);
     lmf_accumulate<G, CPL, lmf_batch<CPL>()>(a, row, x, acc, 0, 0, lmf_negatives(a, n));
     for (int s = a.plan.row_seg[li]; s < a.plan.row_seg[li + 1]; ++s) {
       const float *p = a.ws + (size_t)s * a.C;
@@ -209,7 +192,7 @@ __global__ __launch_bounds__(256) void lmf_finish_kernel(LmfArgs a) {
       for (int k = 0; k < CPL; ++k)
         if (gl + G * k < a.C) acc[k] += p[gl + G * k];
     }
-    lmf_adagrad<G, CPL>(a, row, x, acc);
+    lmf_adagrad<G>(a, gl, row, x, acc);
   }
 }
 
@@ -226,27 +209,11 @@ template <int G, int CPL> static void launch_lmf_pass(const LmfArgs &a, LmfPass 
   else lmf_finish_kernel<G, CPL><<<grid, 256, 0, stream()>>>(a);
 }
 
-// G and the columns per lane from C (the same rule as bpr.hip): 16 lanes up to C = 128, 32 up to 256, 64 up to 1024
+// G by the rule alone (sgd_group.h group_lanes; IMP_BPR_LANES is not read here), so the 12 (G, CPL) it reaches are compiled
 static void launch_lmf(const LmfArgs &a, LmfPass pass, int64_t work) {
-  const int G = a.C <= 128 ? 16 : a.C <= 256 ? 32 : 64;
-  const int cpl = (a.C + G - 1) / G;
+  const int G = group_lanes(a.C);
   const int grid = (int)std::min<int64_t>((work * G + 255) / 256, (int64_t)ctx().num_cus * 8);
-  if (G == 16) {
-    if (cpl <= 1) launch_lmf_pass<16, 1>(a, pass, grid);
-    else if (cpl <= 2) launch_lmf_pass<16, 2>(a, pass, grid);
-    else if (cpl <= 3) launch_lmf_pass<16, 3>(a, pass, grid);
-    else if (cpl <= 4) launch_lmf_pass<16, 4>(a, pass, grid);
-    else if (cpl <= 6) launch_lmf_pass<16, 6>(a, pass, grid);
-    else launch_lmf_pass<16, 8>(a, pass, grid);
-  } else if (G == 32) {
-    if (cpl <= 6) launch_lmf_pass<32, 6>(a, pass, grid);
-    else launch_lmf_pass<32, 8>(a, pass, grid);
-  } else {
-    if (cpl <= 6) launch_lmf_pass<64, 6>(a, pass, grid);
-    else if (cpl <= 8) launch_lmf_pass<64, 8>(a, pass, grid);
-    else if (cpl <= 12) launch_lmf_pass<64, 12>(a, pass, grid);
-    else launch_lmf_pass<64, 16>(a, pass, grid);
-  }
+  for_group_shape<true>(G, a.C, [&](auto g, auto cpl) { launch_lmf_pass<decltype(g)::value, decltype(cpl)::value>(a, pass, grid); });
   IMP_CHECK_HIP(hipGetLastError());
 }
 

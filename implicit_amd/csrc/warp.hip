@@ -25,11 +25,11 @@
 // of (seed, s, nnz, items), but how many candidates a sample examines depends on the factors it meets, so neither the counts
 // nor the factors of a multi-sample call are reproducible.  A single-sample call and a conflict-free call are exact.
 //
-// Layout (pair_sgd.h, shared with bpr.hip): one GROUP of G = 16 / 32 / 64 lanes per sample, lane l owns columns l, l + G,
-// ... (CPL per lane).  The lane's columns of the user row and of the positive row stay in registers for the whole sample;
-// every dot product is a register butterfly inside the group (wave_ops.h group_allsum); no LDS on the sample path.
+// Layout (sgd_group.h, shared with bpr.hip and lmf.hip): one GROUP of G = 16 / 32 / 64 lanes per sample, lane l owns columns
+// l, l + G, ... (CPL per lane).  The lane's columns of the user row and of the positive row stay in registers for the whole
+// sample; every dot product is a register butterfly inside the group (group_dot); no LDS on the sample path.
 // A trial is draw -> liked search -> row load -> dot, each step bound by latency: the candidate's row depends on j alone, so
-// its load is issued before the search (pair_sgd.h group_row_contains) resolves, and a Philox block holds four candidates, so
+// its load is issued before the search (sgd_group.h group_row_contains) resolves, and a Philox block holds four candidates, so
 // the draw of trial t + 1 is a register select that needs nothing from trial t (loading the NEXT candidate's row a trial
 // ahead as well measured 7 - 9 % slower at C = 101 and 129 and is not done: DESIGN 4.15).  The groups of a wavefront need different
 // numbers of trials, so the kernel is ONE loop whose body is one trial step of the group's current sample: a group whose
@@ -37,12 +37,11 @@
 // where the other groups run their next trial.  Every pass consumes a trial, a sample has at most max_sampled of them and
 // s only grows: the loop is bounded by samples x max_sampled, it never waits and shares no flag with another workgroup.
 //
-// Every id the kernel turns into an address has been checked on the device first (check_pair_ids, bpr.hip): an id outside
-// its matrix returns IMP_OUT_OF_RANGE with nothing launched.  j < items by construction.
+// Every id the kernel turns into an address has been checked on the device first (check_pair_ids, pair_sgd.hip): an id
+// outside its matrix returns IMP_OUT_OF_RANGE with nothing launched.  j < items by construction.
 #include "common.h"
-#include "pair_sgd.h"
 #include "philox.h"
-#include "wave_ops.h"
+#include "sgd_group.h"
 
 namespace imp {
 
@@ -69,16 +68,14 @@ struct WarpArgs {
 
 template <int G, int CPL>
 __global__ __launch_bounds__(256) void warp_update_kernel(WarpArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int gl = lane & (G - 1);  // lane inside the group
-  const uint64_t gmask = group_mask<G>(lane);
-  const int64_t ngroups = (int64_t)gridDim.x * (blockDim.x / G);
+  const LaneGroup<G> g;
+  const int gl = g.gl;
   const int C = a.C;
   const float lr = a.lr, reg = a.reg;
   const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
   unsigned long long satisfied = 0, trials = 0;
 
-  int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  int64_t s = g.index;
   // the group's current sample: t trials consumed so far (0: not started), its rows, score and row of the pattern
   int t = 0;
   float *xr = nullptr, *yi = nullptr;
@@ -95,13 +92,13 @@ __global__ __launch_bounds__(256) void warp_update_kernel(WarpArgs a) {
       cand = philox4x32_10(s_lo, s_hi, 1u, 4u, k0, k1);
       lo = a.indptr[u], hi = a.indptr[u + 1];
       xr = a.X + (size_t)u * C, yi = a.Y + (size_t)i * C;
-      float part = 0.f;
 #pragma unroll
-      for (int k = 0; k < CPL; ++k) {
+      for (int k = 0; k < CPL; ++k) {  // the two rows column by column: not two group_loads, which would reorder the loads
         const int c = gl + G * k;
         x[k] = c < C ? xr[c] : 0.f;
         p[k] = c < C ? yi[c] : 0.f;
       }
+      float part = 0.f;
 #pragma unroll
       for (int k = 0; k < CPL; ++k) part = fmaf(x[k], p[k], part);
       sp = group_allsum<G>(part);  // bitwise the same in every lane of the group
@@ -115,17 +112,14 @@ __global__ __launch_bounds__(256) void warp_update_kernel(WarpArgs a) {
     float *yj = a.Y + (size_t)j * C;
     float q[CPL];
 #pragma unroll
-    for (int k = 0; k < CPL; ++k) {  // in flight while the search below runs
+    for (int k = 0; k < CPL; ++k) {  // in flight while the search below runs (group_load here moves 21 kernels' registers)
       const int c = gl + G * k;
       q[k] = c < C ? yj[c] : 0.f;
     }
     if (w == 3 && t < a.max_sampled) cand = philox4x32_10(s_lo, s_hi, 1u + (uint32_t)(t >> 2), 4u, k0, k1);
     bool updated = false;
-    if (!group_row_contains<G>(a.itemids, lo, hi, j, gl, gmask)) {
-      float part = 0.f;
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) part = fmaf(x[k], q[k], part);
-      const float sn = group_allsum<G>(part);
+    if (!group_row_contains<G>(a.itemids, lo, hi, j, gl, g.gmask)) {
+      const float sn = group_dot<G>(x, q);
       if (sn > sp - 1.f) {  // step 4
         const int rank = (a.items - 1) / t;
         const float L = fminf(10.f, logf((float)(rank > 1 ? rank : 1)));
@@ -145,16 +139,12 @@ __global__ __launch_bounds__(256) void warp_update_kernel(WarpArgs a) {
     if (updated || t == a.max_sampled) {  // the sample ends; without an update it is satisfied (step 5)
       satisfied += !updated && gl == 0;
       trials += gl == 0 ? t : 0;
-      s += ngroups;
+      s += g.ngroups;
       t = 0;
     }
   }
 
   block_add_counts(satisfied, trials, a.stats);
-}
-
-template <int G> static void launch_warp(const WarpArgs &a, int grid) {
-  for_columns_per_lane((a.C + G - 1) / G, [&](auto cpl) { warp_update_kernel<G, decltype(cpl)::value><<<grid, 256, 0, stream()>>>(a); });
 }
 
 }  // namespace imp
@@ -165,46 +155,15 @@ extern "C" int imp_warp_update(const imp_intvector *userids, const imp_intvector
                                imp_matrix *Y, float learning_rate, float regularization, int64_t seed, int max_sampled,
                                int64_t samples, int64_t *satisfied, int64_t *trials) {
   return guarded([&] {
-    if (!userids || !itemids || !indptr || !X || !Y || !satisfied || !trials) throw std::invalid_argument("warp_update: NULL argument");
-    if (X->cols != Y->cols) throw std::invalid_argument("X and Y should have the same number of columns");
-    if (X->cols < 2 || X->cols > 1024)
-      throw std::invalid_argument("warp_update: factor matrices need 2 .. 1024 columns (factors + 1 for the item bias)");
-    if (X->itemsize != 4 || Y->itemsize != 4) throw std::invalid_argument("warp_update: factor matrices must be float32");
     if (max_sampled < 1 || max_sampled > 4096) throw std::invalid_argument("warp_update: max_sampled must lie in 1 .. 4096");
-    if (userids->size != itemids->size) throw std::invalid_argument("userids and itemids should have same number of elements");
-    if (indptr->size != X->rows + 1) throw std::invalid_argument("warp_update: indptr must have X.rows + 1 entries");
-    const int64_t nnz = (int64_t)userids->size;
-    if (nnz > INT32_MAX) throw std::invalid_argument("warp_update: more than 2^31 - 1 nonzeros");
-    if (Y->rows > (size_t)INT32_MAX) throw std::invalid_argument("warp_update: more than 2^31 - 1 items");
-    const int64_t n = samples < 0 ? nnz : samples;
-    *satisfied = *trials = 0;
-    if (nnz == 0 || n == 0) return;
-
-    auto &st = ctx().pair_stats;
-    if (st.size < 3) st.alloc(3);
-    unsigned long long *stats = st.data();
-    IMP_CHECK_HIP(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), stream()));
-    check_pair_ids("warp_update", "warp_check_ids", userids, itemids, indptr, X->rows, Y->rows, stats + 2);
-
-    note_device_write(X->data, X->bytes());  // cached top-k planes and padded copies made from X or Y are stale after this
-    note_device_write(Y->data, Y->bytes());
-    WarpArgs a{userids->v.data(), itemids->v.data(), indptr->v.data(), X->f32(), Y->f32(), nnz, n, (uint64_t)seed,
-               learning_rate, regularization, (int)X->cols, (int)Y->rows, max_sampled, stats};
-    {
-      IMP_PROF("warp_update");
-      const int G = bpr_group(a.C);
-      const int cap = ctx().num_cus * 8;  // 8 workgroups of 4 waves per CU: the most the CU holds
-      const int64_t in_flight = hogwild_in_flight(n, X->rows, Y->rows);  // BPR's cap holds for WARP's larger steps: DESIGN 4.15
-      const int grid = (int)std::min<int64_t>((in_flight * G + 255) / 256, cap);
-      if (G == 16) launch_warp<16>(a, grid);
-      else if (G == 32) launch_warp<32>(a, grid);
-      else launch_warp<64>(a, grid);
-      IMP_CHECK_HIP(hipGetLastError());
-    }
-    unsigned long long h[2];
-    IMP_CHECK_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, stream()));
-    sync();  // synchronous in deferred mode too: the counts are the result
-    *satisfied = (int64_t)h[0];
-    *trials = (int64_t)h[1];
+    if (Y && Y->rows > (size_t)INT32_MAX) throw std::invalid_argument("warp_update: more than 2^31 - 1 items");
+    pair_update("warp_update", "warp_check_ids", "warp_update", userids, itemids, indptr, X, Y, samples, satisfied, trials,
+                [&](int G, int grid, int64_t n, unsigned long long *stats) {
+                  const WarpArgs a{userids->v.data(), itemids->v.data(), indptr->v.data(), X->f32(), Y->f32(), (int64_t)userids->size, n,
+                                   (uint64_t)seed, learning_rate, regularization, (int)X->cols, (int)Y->rows, max_sampled, stats};
+                  for_group_shape<false>(G, a.C, [&](auto g, auto cpl) {
+                    warp_update_kernel<decltype(g)::value, decltype(cpl)::value><<<grid, 256, 0, stream()>>>(a);
+                  });
+                });
   });
 }

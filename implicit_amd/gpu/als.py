@@ -330,49 +330,16 @@ class AlternatingLeastSquares(MatrixFactorizationBase):
         return self._XtX0
 
     def to_cpu(self):
-        """implicit/gpu/als.py:300-313: the same model as the reference's CPU class.  This package does not ship a CPU
-        model (the reference's is the parity oracle), so stock `implicit` has to be importable."""
-        try:
-            import implicit.cpu.als as cpu_als
-        except ImportError as e:
-            raise ImportError("to_cpu() builds implicit.cpu.als.AlternatingLeastSquares: install benfred/implicit for the "
-                              "CPU model (implicit_amd ships the MI355X path only)") from e
-        ret = cpu_als.AlternatingLeastSquares(factors=self.factors, regularization=self.regularization, alpha=self.alpha,
-                                              dtype=np.float32, iterations=self.iterations, use_cg=self.use_cg,
-                                              calculate_training_loss=self.calculate_training_loss,
-                                              random_state=self.random_state)
-        ret.user_factors = None if self.user_factors is None else self.user_factors.to_numpy().astype(np.float32)
-        ret.item_factors = None if self.item_factors is None else self.item_factors.to_numpy().astype(np.float32)
-        return ret
+        """implicit/gpu/als.py:300-313: the same model as the reference's CPU class."""
+        return self._cpu_twin("als", "AlternatingLeastSquares", factors=self.factors, regularization=self.regularization,
+                              alpha=self.alpha, dtype=np.float32, iterations=self.iterations, use_cg=self.use_cg,
+                              calculate_training_loss=self.calculate_training_loss, random_state=self.random_state)
 
-    # ---- persistence (same .npz keys as implicit/cpu/als.py:458-477 so stock implicit can load it) ----
-    def save(self, fileobj_or_path):
-        args = {
-            "user_factors": None if self.user_factors is None else self.user_factors.to_numpy(),
-            "item_factors": None if self.item_factors is None else self.item_factors.to_numpy(),
-            "regularization": self.regularization,
-            "factors": self.factors,
-            "iterations": self.iterations,
-            "use_cg": self.use_cg,
-            "cg_steps": self.cg_steps,
-            "calculate_training_loss": self.calculate_training_loss,
-            "dtype": self.dtype.name,
-            "random_state": self.random_state if isinstance(self.random_state, (int, np.integer)) else None,
-            "alpha": self.alpha,
-        }
-        np.savez(fileobj_or_path, **{k: v for k, v in args.items() if v is not None})
-
-    @classmethod
-    def load(cls, fileobj_or_path):
-        model = super().load(fileobj_or_path)
-        for name in ("user_factors", "item_factors"):
-            value = getattr(model, name, None)
-            if isinstance(value, np.ndarray):
-                setattr(model, name, gpu.Matrix(np.ascontiguousarray(value)))
-        for stale in ("num_threads", "use_native"):  # keys written by the CPU model
-            if hasattr(model, stale):
-                delattr(model, stale)
-        return model
+    # ---- persistence (same .npz keys as implicit/cpu/als.py:458-477 so stock implicit can load it; save / load:
+    # MatrixFactorizationBase); num_threads and use_native are keys written by the CPU model ----
+    _npz_keys = ("regularization", "factors", "iterations", "use_cg", "cg_steps", "calculate_training_loss", "dtype",
+                 "random_state", "alpha")
+    _npz_stale = ("num_threads", "use_native")
 
     def __getstate__(self):
         state = super().__getstate__()

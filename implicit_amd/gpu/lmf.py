@@ -2,7 +2,7 @@
 
 The reference has no GPU LMF (implicit/lmf.py raises NotImplementedError for use_gpu=True); this is its CPU model,
 implicit/cpu/lmf.pyx (constructor, fit, save with the same .npz keys without num_threads), trained through one
-imp_lmf_update call per half-sweep (lmf_update, csrc/lmf.hip).  recommend / similar_* / pickling come from
+imp_lmf_update call per half-sweep (lmf_update, csrc/lmf.hip).  recommend / similar_* / save / load / pickling come from
 MatrixFactorizationBase.  Factors have `factors + 2` columns: the item matrix holds 1.0 in column C-1 (a user's C-1 is the
 user bias), the user matrix 1.0 in column C-2 (an item's C-2 is the item bias).
 
@@ -97,43 +97,12 @@ class LogisticMatrixFactorization(MatrixFactorizationBase):
         self._check_fit_errors()
 
     def to_cpu(self):
-        """The same model as the reference's CPU class.  This package does not ship a CPU model, so stock `implicit` has to
-        be importable."""
-        try:
-            import implicit.cpu.lmf as cpu_lmf
-        except ImportError as e:
-            raise ImportError("to_cpu() builds implicit.cpu.lmf.LogisticMatrixFactorization: install benfred/implicit for "
-                              "the CPU model (implicit_amd ships the MI355X path only)") from e
-        ret = cpu_lmf.LogisticMatrixFactorization(factors=self.factors, learning_rate=self.learning_rate,
-                                                  regularization=self.regularization, iterations=self.iterations,
-                                                  neg_prop=self.neg_prop, random_state=self.random_state)
-        ret.user_factors = None if self.user_factors is None else self.user_factors.to_numpy()
-        ret.item_factors = None if self.item_factors is None else self.item_factors.to_numpy()
-        return ret
+        """The same model as the reference's CPU class."""
+        return self._cpu_twin("lmf", "LogisticMatrixFactorization", factors=self.factors, learning_rate=self.learning_rate,
+                              regularization=self.regularization, iterations=self.iterations, neg_prop=self.neg_prop,
+                              random_state=self.random_state)
 
-    # ---- persistence (the .npz keys of implicit/cpu/lmf.pyx save, without num_threads) ----------------
-    def save(self, fileobj_or_path):
-        args = {
-            "user_factors": None if self.user_factors is None else self.user_factors.to_numpy(),
-            "item_factors": None if self.item_factors is None else self.item_factors.to_numpy(),
-            "regularization": self.regularization,
-            "factors": self.factors,
-            "learning_rate": self.learning_rate,
-            "neg_prop": self.neg_prop,
-            "iterations": self.iterations,
-            "dtype": "float32",
-            "random_state": self.random_state if isinstance(self.random_state, (int, np.integer)) else None,
-        }
-        np.savez(fileobj_or_path, **{k: v for k, v in args.items() if v is not None})
-
-    @classmethod
-    def load(cls, fileobj_or_path):
-        model = super().load(fileobj_or_path)
-        for name in ("user_factors", "item_factors"):
-            value = getattr(model, name, None)
-            if isinstance(value, np.ndarray):
-                setattr(model, name, gpu.Matrix(np.ascontiguousarray(value, dtype=np.float32)))
-        for stale in ("num_threads", "dtype"):  # written by the CPU model / not a constructor argument here
-            if hasattr(model, stale):
-                delattr(model, stale)
-        return model
+    # the .npz keys of implicit/cpu/lmf.pyx save, without num_threads; `dtype` is written for the file's readers
+    _npz_keys = ("regularization", "factors", "learning_rate", "neg_prop", "iterations", "dtype", "random_state")
+    _npz_stale = ("num_threads", "dtype")
+    _npz_dtype = np.float32

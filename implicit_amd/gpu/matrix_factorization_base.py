@@ -1,6 +1,7 @@
 """Inference side of the GPU matrix-factorisation models: recommend / similar_items / similar_users
 over KnnQuery.topk.  Same public behaviour as implicit/gpu/matrix_factorization_base.py:12-259
 (which in turn follows implicit/cpu/matrix_factorization_base.py:35-264)."""
+import importlib
 import time
 
 import numpy as np
@@ -204,6 +205,47 @@ class MatrixFactorizationBase(RecommenderBase):
         computed on the device: a NaN anywhere in a row makes that row's norm NaN, and rows x 4 bytes come back instead
         of both factor matrices (0.33 GB at configs[2] -- a fifth of fit()'s set-up time)."""
         self._check_factors(gpu.calculate_norms(self.user_factors).to_numpy(), gpu.calculate_norms(self.item_factors).to_numpy())
+
+    # ---- persistence: the .npz of the reference's CPU models, so stock implicit can load it -----------------
+    _npz_keys = ()  # the hyper-parameters a model's file holds beside user_factors / item_factors, in file order
+    _npz_stale = ()  # keys such a file may hold that are no attribute of the model: written by the CPU model, or for readers
+    _npz_dtype = None  # the dtype factors are loaded as; None: as stored
+
+    def save(self, fileobj_or_path):
+        args = {"user_factors": None if self.user_factors is None else self.user_factors.to_numpy(),
+                "item_factors": None if self.item_factors is None else self.item_factors.to_numpy()}
+        for key in self._npz_keys:
+            args[key] = getattr(self, key, None)
+        args["dtype"] = np.dtype(getattr(self, "dtype", np.float32)).name
+        if not isinstance(self.random_state, (int, np.integer)):
+            args["random_state"] = None
+        np.savez(fileobj_or_path, **{k: v for k, v in args.items() if v is not None})
+
+    @classmethod
+    def load(cls, fileobj_or_path):
+        model = super().load(fileobj_or_path)
+        for name in ("user_factors", "item_factors"):
+            value = getattr(model, name, None)
+            if isinstance(value, np.ndarray):
+                setattr(model, name, gpu.Matrix(np.ascontiguousarray(value, dtype=cls._npz_dtype)))
+        for stale in cls._npz_stale:
+            if hasattr(model, stale):
+                delattr(model, stale)
+        return model
+
+    def _cpu_twin(self, module, name, **kwargs):
+        """to_cpu(): the reference's CPU class implicit.cpu.<module>.<name>(**kwargs) with this model's factors as float32.
+        This package does not ship a CPU model (the reference's is the parity oracle), so stock `implicit` has to be
+        importable."""
+        try:
+            cpu_class = getattr(importlib.import_module(f"implicit.cpu.{module}"), name)
+        except ImportError as e:
+            raise ImportError(f"to_cpu() builds implicit.cpu.{module}.{name}: install benfred/implicit for the "
+                              "CPU model (implicit_amd ships the MI355X path only)") from e
+        ret = cpu_class(**kwargs)
+        ret.user_factors = None if self.user_factors is None else self.user_factors.to_numpy().astype(np.float32)
+        ret.item_factors = None if self.item_factors is None else self.item_factors.to_numpy().astype(np.float32)
+        return ret
 
     # ---- pickling: device arrays travel as numpy (gpu/matrix_factorization_base.py:220-234) --------
     def __getstate__(self):

@@ -1,5 +1,5 @@
-"""The shapes the SGD and ranking-metric GPU tests run at, derived from the launch code of csrc/pair_sgd.h, csrc/bpr.hip,
-csrc/warp.hip, csrc/lmf.hip and csrc/evaluation.hip, and the host-side searches for the inputs those tests need.
+"""The shapes the SGD and ranking-metric GPU tests run at, derived from the launch code of csrc/sgd_group.h, csrc/pair_sgd.hip,
+csrc/bpr.hip, csrc/warp.hip, csrc/lmf.hip and csrc/evaluation.hip, and the host-side searches for the inputs those tests need.
 tests/test_sgd_cases_host.py proves on the CPU that every list covers what it claims.  Test infrastructure only.
 
 DISPATCH_C / LMF_DISPATCH_C: both ends of every (G, CPL) instantiation.  rounds_matrix, bpr_rounds_seed, warp_rounds_case:
@@ -19,32 +19,43 @@ NUM_CUS = 256  # the MI355X; the round counts quoted below hold there and are no
 
 # ---- 1. the dispatch over lanes per sample and columns per lane ---------------------------------------------------------------
 def pair_group(C, lanes=None):
-    """bpr.hip bpr_group:
+    """pair_sgd.hip pair_group_lanes:
         if ((g == 16 || g == 32 || g == 64) && C <= 16 * g) return g;      (g = IMP_BPR_LANES)
-        return C <= 128 ? 16 : C <= 256 ? 32 : 64;"""
+        return group_lanes(C);"""
     if lanes in (16, 32, 64) and C <= 16 * lanes:
         return lanes
+    return group_lanes(C)
+
+
+def group_lanes(C):
+    """sgd_group.h group_lanes: `return C <= 128 ? 16 : C <= 256 ? 32 : 64;`"""
     return 16 if C <= 128 else 32 if C <= 256 else 64
 
 
 def columns_per_lane(cpl):
-    """pair_sgd.h for_columns_per_lane: `if (cpl <= 1) ... else if (cpl <= 2) ... <= 3, <= 4, <= 6, <= 8, <= 12, else 16`."""
+    """sgd_group.h columns_per_lane: `for (int v : {1, 2, 3, 4, 6, 8, 12}) if (cpl <= v) return v;  return 16;`"""
     return next(v for v in (1, 2, 3, 4, 6, 8, 12, 16) if cpl <= v)
 
 
 def pair_instantiation(C, lanes=None):
-    """bpr.hip launch_bpr / warp.hip launch_warp: `for_columns_per_lane((a.C + G - 1) / G, ...)` with G = bpr_group(C)."""
+    """imp_bpr_update / imp_warp_update: `for_group_shape<false>(G, a.C, ...)` with G = pair_group_lanes(C) (pair_sgd.hip
+    pair_update); sgd_group.h for_columns_per_lane: `cpl = columns_per_lane((C + G - 1) / G)`, every one of the 24 pairs
+    compiled."""
     G = pair_group(C, lanes)
     return G, columns_per_lane((C + G - 1) // G)
 
 
 def lmf_instantiation(C):
-    """lmf.hip launch_lmf: `G = a.C <= 128 ? 16 : a.C <= 256 ? 32 : 64;  cpl = (a.C + G - 1) / G;` then its own chains:
-    G = 16: cpl <= 1, 2, 3, 4, 6, else 8;  G = 32: cpl <= 6, else 8;  G = 64: cpl <= 6, 8, 12, else 16."""
-    G = 16 if C <= 128 else 32 if C <= 256 else 64
-    cpl = (C + G - 1) // G
-    chain = {16: (1, 2, 3, 4, 6), 32: (6,), 64: (6, 8, 12)}[G]
-    return G, next((v for v in chain if cpl <= v), {16: 8, 32: 8, 64: 16}[G])
+    """lmf.hip launch_lmf: `G = group_lanes(a.C);  for_group_shape<true>(G, a.C, ...)`: the dispatcher of the pairwise
+    kernels under the rule alone (IMP_BPR_LANES is not read), compiled for the pairs `rule_reaches` (sgd_group.h) only."""
+    G = group_lanes(C)
+    return G, columns_per_lane((C + G - 1) // G)
+
+
+def rule_reaches(G, CPL):
+    """sgd_group.h rule_reaches: `for (int C = 1; C <= 1024; ++C) if (group_lanes(C) == G && columns_per_lane((C + G - 1) /
+    G) == CPL) return true;  return false;`"""
+    return any(group_lanes(C) == G and columns_per_lane((C + G - 1) // G) == CPL for C in range(1, 1025))
 
 
 INSTANTIATIONS = [(16, 1), (16, 2), (16, 3), (16, 4), (16, 6), (16, 8), (32, 6), (32, 8), (64, 6), (64, 8), (64, 12), (64, 16)]
@@ -70,7 +81,7 @@ DISPATCH_C = _with_ends([2, 17, 33, 65, 101, 129, 257, 1024], pair_instantiation
 LMF_EXISTING_C = [3, 5, 32, 34, 66, 130, 1024]
 LMF_DISPATCH_C = _with_ends(LMF_EXISTING_C, lmf_instantiation, LMF_MIN_C)
 
-# IMP_BPR_LANES (read per call in bpr_group): (lanes, C, the instantiation it must reach).  The first five and the last are
+# IMP_BPR_LANES (read per call in pair_group_lanes): (lanes, C, the instantiation it must reach).  The first five and the last are
 # the cases the switch was first tested at; with the others every instantiation that only the switch reaches is launched:
 # <16, 12>, <16, 16>, <32, 1 .. 4>, <32, 12>, <32, 16>, <64, 1 .. 4>.  The last one must be ignored: C > 16 * lanes.
 LANE_OVERRIDES = [(32, 17, (32, 1)), (64, 17, (64, 1)), (32, 64, (32, 2)), (64, 64, (64, 1)), (64, 129, (64, 3)),
@@ -80,7 +91,7 @@ LANE_OVERRIDES = [(32, 17, (32, 1)), (64, 17, (64, 1)), (32, 64, (32, 2)), (64, 
 
 
 def hogwild_in_flight(samples, users, items):
-    """pair_sgd.h: `std::min<int64_t>(samples, std::max<int64_t>(16, (int64_t)std::min(users, items) / 16))`."""
+    """sgd_group.h: `std::min<int64_t>(samples, std::max<int64_t>(16, (int64_t)std::min(users, items) / 16))`."""
     return min(samples, max(16, min(users, items) // 16))
 
 
@@ -145,7 +156,7 @@ def warp_rounds_case(m, rows, C, n=ROUNDS_N, max_sampled=ROUNDS_MAX_SAMPLED):
 
 
 # ---- 3. whole epochs at zero learning rate: the search-cut matrix -----------------------------------------------------------
-# group_row_contains (pair_sgd.h) runs `while (hi - lo > G)` with slices of ceil((hi - lo) / G): no splitter level up to G
+# group_row_contains (sgd_group.h) runs `while (hi - lo > G)` with slices of ceil((hi - lo) / G): no splitter level up to G
 # entries, one up to G^2, two above.  Row lengths on both sides of G and G^2 for G = 16, 32, 64 (and the lengths next to them):
 SEARCH_LENGTHS = [1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097]
 # short rows are the user of few samples (a sample picks its user by nonzero), so they are repeated

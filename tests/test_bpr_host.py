@@ -74,5 +74,6 @@ def test_gpu_bpr_module_imports_without_device():
         import implicit_amd.bpr  # noqa: F401
         import implicit_amd.gpu as g
         import implicit_amd.gpu.bpr as b
+        from implicit_amd.gpu.matrix_factorization_base import MatrixFactorizationBase
 
-    assert callable(g.bpr_epoch) and issubclass(b.BayesianPersonalizedRanking, b.MatrixFactorizationBase)
+    assert callable(g.bpr_epoch) and issubclass(b.BayesianPersonalizedRanking, MatrixFactorizationBase)

@@ -31,6 +31,8 @@ def test_dispatch_ends_are_the_ranges_of_the_launch_code():
     assert sc.dispatch_ends(sc.lmf_instantiation, sc.LMF_MIN_C) == want
     # the two restatements agree wherever both entry points accept C
     assert all(sc.pair_instantiation(C) == sc.lmf_instantiation(C) for C in range(3, 1025))
+    # what the dispatcher compiles for LMF (rule_reaches) is the twelve pairs the rule picks, no more
+    assert {(G, CPL) for G in (16, 32, 64) for CPL in (1, 2, 3, 4, 6, 8, 12, 16) if sc.rule_reaches(G, CPL)} == set(sc.INSTANTIATIONS)
     # the values the tests ran at before are still there
     assert {2, 17, 33, 65, 101, 129, 257, 1024} <= set(sc.DISPATCH_C) and set(sc.LMF_EXISTING_C) <= set(sc.LMF_DISPATCH_C)
     # a C with one wholly masked register: cpl = 5 on CPL = 6 and cpl = 7 on CPL = 8

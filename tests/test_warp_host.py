@@ -116,7 +116,8 @@ def test_gpu_warp_module_imports_without_device():
         import implicit_amd.warp  # noqa: F401
         import implicit_amd.gpu as g
         import implicit_amd.gpu.warp as w
+        from implicit_amd.gpu.matrix_factorization_base import MatrixFactorizationBase
 
-    assert callable(g.warp_epoch) and issubclass(w.WARPMatrixFactorization, w.MatrixFactorizationBase)
+    assert callable(g.warp_epoch) and issubclass(w.WARPMatrixFactorization, MatrixFactorizationBase)
     assert not hasattr(w.WARPMatrixFactorization, "to_cpu")  # no CPU counterpart to return
-    assert w.WARPMatrixFactorization.recalculate_user is w.MatrixFactorizationBase.recalculate_user  # the base's: it raises
+    assert w.WARPMatrixFactorization.recalculate_user is MatrixFactorizationBase.recalculate_user  # the base's: it raises
