@@ -246,9 +246,10 @@ def test_cholesky_sweep_beyond_256_factors(gpu, oracle, f):
     assert err < TOL
     assert not got[5].any()
     if f == 320:                                      # not positive definite -> ValueError naming the row, as below
-        with pytest.raises(ValueError):
+        with pytest.raises(ValueError) as info:
             solver.least_squares_cholesky(gpu.CSRMatrix(C), gpu.Matrix(X0), gpu.Matrix.zeros(f, f),
                                           gpu.Matrix(np.zeros_like(Y0)), 0.0)
+        assert C.indptr[1] > C.indptr[0] and info.value.failed_row == 0   # every non-empty row fails: row 0 is the smallest
 
 
 def test_cholesky_not_positive_definite_raises(gpu):

@@ -83,11 +83,12 @@ def _inputs(f, storage, rows):
     return C, X0, Y0
 
 
-def solve(gpu, case):
-    """The half sweep of `case` on the GPU: (X after the call, the gramian the solver was handed)."""
+def solve(gpu, case, solver=None):
+    """The half sweep of `case` on the GPU: (X after the call, the gramian the solver was handed).  `solver`: a solver object that
+    has been used before (tests/test_gpu_cholesky_edges.py: right after a failing call), instead of a new one."""
     solver_kind, f, storage, steps, rows = case
     C, X0, Y0 = _inputs(f, storage, rows)
-    solver = gpu.LeastSquaresSolver()
+    solver = solver or gpu.LeastSquaresSolver()
     Xd, Yd, gram = gpu.Matrix(X0), gpu.Matrix(Y0), gpu.Matrix.zeros(f, f)
     if solver_kind == "cg":
         solver.calculate_yty(Yd, gram, REG)
@@ -118,10 +119,10 @@ def expected(oracle, case, gram):
     return _WANT[case]
 
 
-def check(gpu, oracle, case):
+def check(gpu, oracle, case, solver=None):
     solver_kind, f, storage, steps, rows = case
     C, X0, _ = _inputs(f, storage, rows)
-    got, gram = solve(gpu, case)
+    got, gram = solve(gpu, case, solver)
     want = expected(oracle, case, gram)
     n = C.shape[0]
     assert got.dtype == X0.dtype and got.shape == X0.shape
