@@ -346,7 +346,9 @@ extern "C" int imp_spmat_create(int32_t rows, int32_t cols, int64_t nnz, const i
     bool unique = true;
     std::vector<int32_t> mark(cols, -1);
     for (int32_t r = 0; r < rows; ++r) {
-      if (indptr[r + 1] < indptr[r]) throw std::invalid_argument("spmat_create: indptr must be non-decreasing");
+      // checked before the row is read: an offset beyond nnz would lead the loop below past the end of indices
+      if (indptr[r + 1] < indptr[r] || indptr[r + 1] > nnz)
+        throw std::invalid_argument("spmat_create: indptr must be non-decreasing and end at nnz");
       for (int64_t p = indptr[r]; p < indptr[r + 1]; ++p) {
         const int32_t c = indices[p];
         if (c < 0 || c >= cols) throw std::invalid_argument("spmat_create: column id out of range");

@@ -15,8 +15,8 @@ def product_topk(A, B, k, zero_own=False, chunk_pairs=1 << 24):
     scores = np.full((R, k), -np.inf)
     counts = np.zeros(R, dtype=np.int32)
     blen = np.diff(B.indptr)
-    work = np.add.reduceat(blen[A.indices], A.indptr[:-1]) if A.nnz else np.zeros(R, np.int64)
-    work = np.where(np.diff(A.indptr) > 0, work, 0)
+    # pairs per row, for the chunking alone (prefix sums: reduceat rejects the offsets of trailing empty rows)
+    work = np.diff(np.concatenate([[0], np.cumsum(blen[A.indices], dtype=np.int64)])[A.indptr])
     r0 = 0
     while r0 < R:
         r1, acc = r0, 0
