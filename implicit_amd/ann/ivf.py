@@ -43,7 +43,8 @@ class IVFModel(RecommenderBase):
     model : a fitted-or-not matrix-factorisation model of this package (item_factors / user_factors on the device)
     approximate_similar_items, approximate_recommend : build and use the index for that call; otherwise the exact model
     nlist : lists of the index (clamped to the item count, with a ParameterWarning)
-    nprobe : lists scanned per query
+    nprobe : lists scanned per query; above nlist it means nlist, but min(nprobe, nlist) > 1024 makes every search raise
+        ValueError (IVFIndex.search probes at most 1024 lists)
     iterations : k-means rounds of the index build
     random_state : seed of the numpy Generator that draws the initial centroids (None: unseeded)
 

@@ -696,9 +696,9 @@ extern "C" int imp_ivf_search(imp_ivf *ix, const imp_matrix *query, int k, int n
     if (query->itemsize != 4 && query->itemsize != 2) throw std::invalid_argument("ivf_search: queries must be fp32 or fp16");
     if (query->cols != ix->f) throw std::invalid_argument("ivf_search: the queries' column count differs from the index's");
     const size_t nq = query->rows;
-    if (!nq) return;
     const int nlist = ix->nlist, f_pad = ix->f_pad, P = std::min(nprobe, nlist);
-    if (P > kIvfMaxK) throw std::invalid_argument("ivf_search: no more than 1024 lists can be probed");
+    if (P > kIvfMaxK) throw std::invalid_argument("ivf_search: no more than 1024 lists can be probed");  // zero queries too
+    if (!nq) return;
     int kpad = 1;
     while (kpad < k) kpad <<= 1;
     // a query's share of the temporaries, its scores at worst those of the P longest lists

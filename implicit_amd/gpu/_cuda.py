@@ -774,7 +774,10 @@ class IVFIndex:
     def search(self, queries, k, nprobe, return_probes=False):
         """(ids int32, scores float32), each queries x k, best first under (score desc, id desc); where the probed lists hold
         fewer than k vectors the tail is (-1, -FLT_MAX).  nprobe above nlist is nlist.  return_probes adds the
-        queries x min(nprobe, nlist) probed list ids.  k outside 1 .. 1024 or nprobe < 1 raise ValueError."""
+        queries x min(nprobe, nlist) probed list ids.  k outside 1 .. 1024 or nprobe < 1 raise ValueError.  So does
+        min(nprobe, nlist) > 1024: a search probes at most 1024 lists, and an index of more lists refuses a larger nprobe
+        instead of clamping it, whatever the number of queries (zero included); the refusal touches neither the index nor
+        its temporaries.  Zero queries give two (0, k) arrays."""
         if not isinstance(queries, Matrix):
             queries = Matrix(queries)
         k, nprobe = int(k), int(nprobe)

@@ -1,5 +1,6 @@
 """Float64 numpy restatement of the IVF-Flat index, written from its specification: spherical
-k-means from given initial rows, the inverted lists, and the probed search.  Orders are total: (score desc, id desc)."""
+k-means from given initial rows, the inverted lists, and the probed search.  Orders are total: (score desc, id desc).
+The exact_* functions at the end restate the `iterations = 0` build and the search in integers, for inputs that have one answer."""
 import numpy as np
 
 
@@ -117,3 +118,75 @@ def audit(got_ids, want_ids, want_scores, score_of, f):
         assert abs(exact - want) <= tol * max(abs(want), 1e-30), f"id at {pos} differs and is not a near-tie ({exact} vs {want})"
         exceptions += 1
     return exceptions
+
+
+# ---- exact restatements ------------------------------------------------------------------------------------------------
+# Integer-valued vectors and queries whose scores stay below 2^24 have one possible fp32 score in any summation order, and
+# an `iterations = 0` build whose initial rows are zero or +-2^m e_j has the centroids 0 / +-e_j exactly (the sum of squares
+# 4^m, its square root and the division are exact).  Everything below is integer arithmetic on such inputs: one answer,
+# compared with array_equal.
+def exact_centroids(vectors, init_rows):
+    """(coord[nlist], sign[nlist]): centroid c is sign[c] * e_coord[c] (sign 0: the zero centroid of a zero row)."""
+    rows = np.asarray(vectors)[np.asarray(init_rows)].astype(np.int64)
+    assert ((rows != 0).sum(axis=1) <= 1).all(), "an initial row is not one-hot"
+    coord = np.abs(rows).argmax(axis=1)
+    value = rows[np.arange(len(rows)), coord]
+    mag = np.abs(value)
+    assert ((mag & (mag - 1)) == 0).all(), "an initial row's entry is not a power of two"
+    return coord, np.sign(value)
+
+
+def exact_centroid_matrix(coord, sign, f):
+    cent = np.zeros((len(coord), f), dtype=np.float32)
+    cent[np.arange(len(coord)), coord] = sign
+    return cent
+
+
+def exact_build(vectors, init_rows):
+    """(coord, sign, assign[n], offsets[nlist + 1], ids[n]) of the iterations = 0 build: a vector's score against list c is
+    sign[c] * v[coord[c]], ties go to the larger list id, ids ascend inside a list."""
+    v = np.asarray(vectors).astype(np.int64)
+    coord, sign = exact_centroids(v, init_rows)
+    assign = argmax_rows(v[:, coord] * sign)
+    offsets, ids = build_lists(assign, len(coord))
+    return coord, sign, assign, offsets, ids
+
+
+def exact_scores(vectors, queries):
+    """queries x vectors int64 inner products.  The product runs in float64, where sums of integers below 2^53 are exact in
+    any order; the result is checked to be integral and below 2^24 (exact in fp32 too)."""
+    s = np.asarray(queries, dtype=np.float64) @ np.asarray(vectors, dtype=np.float64).T
+    assert (s == np.rint(s)).all() and (np.abs(s) < 2.0 ** 24).all()
+    return s.astype(np.int64)
+
+
+def exact_probes(coord, sign, queries, nprobe):
+    """queries x min(nprobe, nlist) list ids under (coarse score desc, list id desc); the coarse score is sign * q[coord]."""
+    q = np.asarray(queries).astype(np.int64)
+    nlist = len(coord)
+    key = q[:, coord] * sign * nlist + np.arange(nlist)  # distinct per row: one order
+    return np.argsort(-key, axis=1, kind="stable")[:, :min(nprobe, nlist)]
+
+
+def exact_search(coord, sign, assign, vectors, queries, k, nprobe, probes=None):
+    """(probes, ids [q x k] int64, scores [q x k] float64): the k best vectors of the probed lists under (score desc, id
+    desc), holes (-1, -FLT_MAX).  Vectorised over the queries.  `probes` given: scan those lists."""
+    v = np.asarray(vectors)
+    n, nlist, nq = len(v), len(coord), len(queries)
+    if probes is None:
+        probes = exact_probes(coord, sign, queries, nprobe)
+    probes = np.asarray(probes)
+    probed = np.zeros((nq, nlist), dtype=bool)
+    np.put_along_axis(probed, probes.astype(np.int64), True, axis=1)
+    hole = -(1 << 62)  # below every key: |score * n + id| < 2^24 * 2^31
+    key = np.where(probed[:, np.asarray(assign)], exact_scores(v, queries) * n + np.arange(n), hole)
+    kk = min(k, n)
+    if kk < n:  # the kk largest keys of every row, then only those sorted
+        key = np.take_along_axis(key, np.argpartition(-key, kk - 1, axis=1)[:, :kk], axis=1)
+    pkey = -np.sort(-key, axis=1)
+    out_ids = np.full((nq, k), -1, dtype=np.int64)
+    out_scores = np.full((nq, k), -float(np.finfo(np.float32).max))
+    filled = pkey != hole
+    out_ids[:, :kk][filled] = (pkey % n)[filled]
+    out_scores[:, :kk][filled] = (pkey // n)[filled]
+    return probes, out_ids, out_scores
