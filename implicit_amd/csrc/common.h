@@ -222,6 +222,8 @@ struct Context {
   DeviceArray<double> knn_acc;                   // dense per-worker accumulators of sparse_topk_product, kept at a sentinel (knn.hip)
   DeviceArray<int32_t> knn_touched;              // the workers' touched-column lists (knn.hip)
   int knn_cols = -1;                             // column count knn_acc is laid out for
+  DeviceArray<float> subspace_pred;              // predictions of a subspace half sweep, one per nonzero in CSR order (als_subspace.hip)
+  DeviceArray<float> subspace_ws;                // its long rows' segment partials, block steps and failure flags
 };
 inline hipStream_t stream() { return ctx().stream; }
 // a C-ABI entry point is about to write `bytes` at `dst` through the library (or the memory is being freed): a padded copy of Y

@@ -442,6 +442,8 @@ int imp_release_workspaces(void) {
     c.pad.release();
     c.nm_fix_rows = {};
     c.w256_ws = {};
+    c.subspace_pred = {};
+    c.subspace_ws = {};
     std::lock_guard<std::mutex> g(c.small_mutex);
     for (auto &list : c.small_free) {
       for (void *p : list) (void)hipFree(p);

@@ -14,6 +14,8 @@ void gramian_half(const void *Y, long n_rows, int f, float reg, float *out);    
 bool cg_native_half(int f);                                                                                 // als_cg.hip
 void least_squares_cg(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, int cg_steps);  // als_cg.hip
 int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg);
+int64_t least_squares_subspace(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg, int block_size,
+                               int sweeps);  // als_subspace.hip
 
 // K7: loss numerator terms, one wavefront per user row (oracle: implicit/cpu/_als.pyx:257-308):
 //   r = YtY x + sum_k ((c>0 ? -2c : 0) + (|c|-1) y.x) y ;  loss += r.x + sum |c| ; user_norm += x.x
@@ -249,6 +251,30 @@ int imp_solver_least_squares_cholesky(imp_solver *, const imp_csr *cui, imp_matr
     if (failed >= 0)
       throw std::invalid_argument("cholesky factorisation failed on row " + std::to_string(failed) +
                                   ". Try increasing the regularization parameter.");
+  });
+}
+
+int imp_solver_least_squares_subspace(imp_solver *, const imp_csr *cui, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y,
+                                      double regularization, int block_size, int sweeps, int64_t *failed_row) {
+  return guarded([&] {
+    if (failed_row) *failed_row = -1;
+    if (X->itemsize != 4 || Y->itemsize != 4) throw std::invalid_argument("least_squares_subspace: X and Y must be float32");
+    check_solver_args(cui, X, YtY, Y);
+    if (X->cols > 1024) throw std::invalid_argument("least_squares_subspace: factors must be <= 1024");
+    if (block_size < 1 || block_size > 32) throw std::invalid_argument("least_squares_subspace: block_size must be 1 .. 32");
+    if (sweeps < 1) throw std::invalid_argument("least_squares_subspace: sweeps must be >= 1");
+    note_device_write(X->data, (size_t)cui->rows * X->cols * X->itemsize);  // the rows this call solves
+    int64_t failed = -1;
+    size_t block = 0;
+    for_each_part(cui, X, [&](const imp_csr *part, const imp_matrix *xp) {
+      const int64_t bad = least_squares_subspace(part, const_cast<imp_matrix *>(xp), YtY, Y, regularization, block_size, sweeps);
+      if (bad >= 0 && failed < 0) failed = bad + (cui->parts.empty() ? 0 : cui->part_row0[block]);
+      ++block;
+    });
+    if (failed_row) *failed_row = failed;
+    if (failed >= 0)
+      throw std::invalid_argument("subspace step failed on row " + std::to_string(failed) +
+                                  ": a block's matrix is not positive definite. Try increasing the regularization parameter.");
   });
 }
 

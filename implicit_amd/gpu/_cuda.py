@@ -376,6 +376,20 @@ class LeastSquaresSolver:
             e.failed_row = failed.value  # -1 unless the factorisation itself failed (then: the smallest failing row)
             raise
 
+    def least_squares_subspace(self, cui, X, YtY, Y, regularization, block_size, sweeps=1):
+        """NEW: the block-subspace half sweep of iALS++ for large factor counts: every row of X is improved, from its stored
+        value, one block of `block_size` (1 .. 32) coordinates at a time by an exact Newton step in that block, `sweeps`
+        times over.  YtY is the UNregularised gramian; float32 X and Y, at most 1024 factors.  block_size >= factors is the
+        exact solve of least_squares_cholesky.  Raises ValueError (with .failed_row, -1 for an argument error) when a
+        block's matrix is not positive definite; the other rows are solved."""
+        failed = ctypes.c_int64(-1)
+        try:
+            check(lib().imp_solver_least_squares_subspace(self._h, cui._h, X._h, YtY._h, Y._h, float(regularization),
+                                                          int(block_size), int(sweeps), ctypes.byref(failed)))
+        except ValueError as e:
+            e.failed_row = failed.value
+            raise
+
     def explain_factor(self, cui, YtY, Y, regularization, weights):
         """NEW: the Cholesky factor L of every row's A_u = YtY + regularization I + sum (|c| - 1) y y^T (YtY UNregularised, the
         matrix of least_squares_cholesky) into rows [u f, (u + 1) f) of `weights`, a float32 (cui.rows * f) x f Matrix: lower

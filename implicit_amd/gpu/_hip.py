@@ -76,6 +76,9 @@ _SIGNATURES = {
                                  ctypes.c_void_p, ctypes.c_int],
     "imp_solver_least_squares_cholesky": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)],
+    "imp_solver_least_squares_subspace": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int64)],
     "imp_solver_calculate_loss": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_float, c_f32_p],
     "imp_solver_explain_factor": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,

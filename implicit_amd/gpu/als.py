@@ -13,6 +13,9 @@ numerics of the reference's *CPU* path, which is the parity oracle (implicit/cpu
   * `use_cg=False` selects the Cholesky solver (cpu/als.py:418-423), which the reference GPU path
     does not have; recalculate_user/item use Cholesky as the CPU path does (cpu/als.py:221-241)
     (any factors <= 1024; the reference GPU path runs CG to `factors` steps there, gpu/als.py:188-195);
+  * `block_size=k` (1 .. 32, with `subspace_sweeps`) replaces the CG half sweep of fit() by the block-subspace solver of
+    iALS++ (csrc/als_subspace.hip; no reference counterpart): meant for factors >= 256, float32 factors, one GPU,
+    use_cg=True; block_size=None is the CG / Cholesky path, bit for bit;
   * NaN factors after fit raise ModelFitError (cpu/als.py:202).
 
 Multi-GPU: `AlternatingLeastSquares(..., comm=implicit_amd.gpu.Comm(...))`, one process per GPU, every rank calling
@@ -41,9 +44,23 @@ _EXPLAIN_MAX_FACTORS = 256     # explain / explain_batch: the triangle stays in 
 
 class AlternatingLeastSquares(MatrixFactorizationBase):
     def __init__(self, factors=64, regularization=0.01, alpha=1.0, dtype=np.float32, iterations=15,
-                 calculate_training_loss=False, random_state=None, use_cg=True, cg_steps=3, init="numpy", comm=None):
+                 calculate_training_loss=False, random_state=None, use_cg=True, cg_steps=3, init="numpy", comm=None,
+                 block_size=None, subspace_sweeps=1):
         if not gpu.HAS_CUDA:
             raise ValueError("No usable HIP device / extension, can't train on GPU.")
+        if block_size is not None:
+            # the block-subspace solver of iALS++ takes the place of the CG half sweep in fit()
+            if not 1 <= int(block_size) <= 32:
+                raise ValueError("block_size must be between 1 and 32")
+            if int(subspace_sweeps) < 1:
+                raise ValueError("subspace_sweeps must be >= 1")
+            if not use_cg:
+                raise ValueError("block_size replaces the CG half sweep: it cannot be combined with use_cg=False")
+            if np.dtype(dtype) != np.float32:
+                raise ValueError("the block-subspace solver (block_size) keeps float32 factors")
+            if comm is not None and comm.nranks > 1:
+                raise ValueError("the block-subspace solver (block_size) runs on one GPU: no multi-rank comm")
+            block_size, subspace_sweeps = int(block_size), int(subspace_sweeps)
         super().__init__()
         self.factors = factors
         self.regularization = regularization
@@ -56,6 +73,8 @@ class AlternatingLeastSquares(MatrixFactorizationBase):
         self.cg_steps = cg_steps
         self.init = init
         self.comm = comm
+        self.block_size = block_size
+        self.subspace_sweeps = subspace_sweeps
         self.fit_callback = None
         self._solver = None
         self._YtY = self._XtX = None      # regularised gramians (the reference's cached properties)
@@ -181,7 +200,10 @@ class AlternatingLeastSquares(MatrixFactorizationBase):
 
     def _half_sweep(self, C, X, Y, gram):
         """One half iteration: X <- argmin given Y (gramian + per-row solves)."""
-        if self.use_cg:
+        if getattr(self, "block_size", None) is not None:
+            self.solver.calculate_yty(Y, gram, 0.0)
+            self.solver.least_squares_subspace(C, X, gram, Y, self.regularization, self.block_size, self.subspace_sweeps)
+        elif self.use_cg:
             self.solver.calculate_yty(Y, gram, self.regularization)
             self.solver.least_squares(C, X, gram, Y, self.cg_steps)
         else:

@@ -79,7 +79,8 @@ int imp_device_synchronize(void);
 int imp_solver_fixup_rows(unsigned long long *count, int reset);
 int imp_mem_get_info(size_t *free_bytes, size_t *total_bytes);
 /* NEW: frees the per-device scratch buffers the solver paths grow on demand (split-K gramian partials, long-row CG state, the
- * zero-padded copies other factor counts ride the f = 64 / 128 / 256 kernels on, cluster exchange slots); the next call that
+ * zero-padded copies other factor counts ride the f = 64 / 128 / 256 kernels on, cluster exchange slots, the predictions and
+ * segment partials of imp_solver_least_squares_subspace); the next call that
  * needs one allocates it again.  fit() calls it when it returns. */
 int imp_release_workspaces(void);
 const char *imp_version(void);
@@ -195,6 +196,21 @@ int imp_solver_least_squares(imp_solver *s, const imp_csr *cui, imp_matrix *X, c
 int imp_solver_least_squares_cholesky(imp_solver *s, const imp_csr *cui, imp_matrix *X,
                                       const imp_matrix *YtY, const imp_matrix *Y,
                                       double regularization, int64_t *failed_row);
+/* NEW (no reference counterpart): the block-subspace half sweep of iALS++ (Rendle, Krichene, Zhang, Koren 2021) for large
+ * factor counts.  fp32 X and Y, f <= 1024, 1 <= block_size <= 32, sweeps >= 1; YtY is UNregularised.  With w_j = |c_j| - 1 and
+ * c+_j = max(c_j, 0) a row's system is A x = b, A = YtY + regularization I + sum_j w_j y_j y_j^T, b = sum_j c+_j y_j, as in
+ * imp_solver_least_squares_cholesky.  A sweep starts from the stored x (warm start): p_j = x . y_j for every stored entry; then
+ * for the blocks S = [0, k), [k, 2k), ... in order (k = block_size, the last one possibly shorter)
+ *   g = (YtY x)_S + regularization x_S + sum_j (w_j p_j - c+_j) y_j[S],  H = YtY_SS + regularization I + sum_j w_j y_j[S] y_j[S]^T,
+ *   delta = -H^-1 g by Cholesky,  x_S += delta,  p_j += delta . y_j[S];
+ * sweeps > 1 repeats the block loop without recomputing p.  block_size >= f is the exact solve.  Empty rows become zero.  A
+ * non-positive pivot in any block of any row returns IMP_INVALID_ARGUMENT with *failed_row = the smallest such row (else -1);
+ * the other rows are solved, a failing row's contents are unspecified.  No floating-point atomics: equal inputs give bitwise
+ * equal outputs.  Argument errors are reported before any launch.  Waits for its result also in deferred-sync mode, as
+ * imp_solver_least_squares_cholesky does. */
+int imp_solver_least_squares_subspace(imp_solver *s, const imp_csr *cui, imp_matrix *X, const imp_matrix *YtY,
+                                      const imp_matrix *Y, double regularization, int block_size, int sweeps,
+                                      int64_t *failed_row);
 /* calculate_loss(Cui, X, Y, regularization) (als.cu:253-281; oracle _als.pyx:257-308). */
 int imp_solver_calculate_loss(imp_solver *s, const imp_csr *cui, const imp_matrix *X,
                               const imp_matrix *Y, float regularization, float *loss_out);
