@@ -30,10 +30,6 @@
 
 namespace imp {
 
-template <typename T> void least_squares_cg_q(const imp_csr *C, T *X, const T *Y, const float *A0, int f, int cg_steps);  // als_cg_q.hip
-void least_squares_cg_w256(const imp_csr *C, float *X, const float *Y, const float *A0, int cg_steps);  // als_cg_w256.hip
-template <typename T> void least_squares_cg_nm(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int f, int cg_steps);  // als_cg_nm.hip
-
 // ---- generic per-nnz pass (any f): 4 gathers in flight, one DPP all-reduce per dot -------------------
 template <int VPL, bool VEC, bool FIRST>
 __device__ __forceinline__ void sparse_pass_simple(const int32_t *__restrict__ indices, const float *__restrict__ data,
@@ -552,8 +548,7 @@ static void launch_fused(const imp_csr *C, int first, int count, float *X, const
   constexpr int LD = 64 * VPL;
   size_t lds = (A_LDS ? (size_t)f * LD : 0) * sizeof(float);
   auto kern = als_cg_kernel<VPL, BLOCK, A_LDS>;
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)std::max<size_t>(lds, 16)));
+  allow_dynamic_lds(kern, std::max<size_t>(lds, 16));
   int blocks_per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / BLOCK, (160 * 1024) / std::max<size_t>(lds, 1)));
   int grid = std::min((count + BLOCK / 64 - 1) / (BLOCK / 64), ctx().num_cus * blocks_per_cu * ctx().oversub);
   IMP_PROF(name);
@@ -570,9 +565,7 @@ static void launch_long(const imp_csr *C, const LongPlan &lp, T *X, const T *Y, 
   constexpr int LD = 64 * VPL;
   constexpr bool kHalf = !std::is_same<T, float>::value;
   size_t need = ((size_t)n_seg + (kHalf ? 3 : 2) * (size_t)n_long) * LD + 2 * (size_t)n_long;
-  auto &ws = ctx().long_ws;
-  if (ws.size < need) ws.alloc(need);
-  float *partial = ws.data();
+  float *partial = ctx().long_ws.reserve(need);
   float *rvec = partial + (size_t)n_seg * LD;
   float *pvec = rvec + (size_t)n_long * LD;
   float *scal = pvec + (size_t)n_long * LD;
@@ -584,10 +577,8 @@ static void launch_long(const imp_csr *C, const LongPlan &lp, T *X, const T *Y, 
   size_t lds = ((A_LDS ? (size_t)f * LD : 0) + (rowblock ? (size_t)(BLOCK / 64) * LD : 0)) * sizeof(float);
   auto comb0 = rowblock ? cg_long_combine_kernel<VPL, VEC, BLOCK, A_LDS, 0, true, T> : cg_long_combine_kernel<VPL, VEC, BLOCK, A_LDS, 0, false, T>;
   auto comb1 = rowblock ? cg_long_combine_kernel<VPL, VEC, BLOCK, A_LDS, 1, true, T> : cg_long_combine_kernel<VPL, VEC, BLOCK, A_LDS, 1, false, T>;
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(comb0), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)std::max<size_t>(lds, 16)));
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(comb1), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)std::max<size_t>(lds, 16)));
+  allow_dynamic_lds(comb0, std::max<size_t>(lds, 16));
+  allow_dynamic_lds(comb1, std::max<size_t>(lds, 16));
   int grid_part = std::min(((n_seg + 3) / 4 + 7) / 8 * 8, ctx().num_cus * 8);  // a multiple of 8: blockIdx % 8 = XCD
   int grid_comb = rowblock ? n_long : std::min((n_long + BLOCK / 64 - 1) / (BLOCK / 64), ctx().num_cus * 2);
   {

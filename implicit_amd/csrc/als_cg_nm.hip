@@ -857,19 +857,17 @@ template <int F, typename T> void launch_nm(const imp_csr *C, T *X, const T *Y, 
   static_assert(L::IMG % 4 == 0, "the image is copied in 16-byte pieces");
   const size_t lds = L::lds_floats * sizeof(float);
   const int n_multi = C->nm_multi_rows, n_multi_seg = C->nm_multi_segs;
-  auto &ws = ctx().long_ws;
   const size_t need = (size_t)L::IMG + (size_t)n_multi_seg * (L::IMG + F);  // gramian image | partial images
-  if (ws.size < need) ws.alloc(need);
-  float *gram_img = ws.data(), *partial = gram_img + L::IMG;
+  float *gram_img = ctx().long_ws.reserve(need), *partial = gram_img + L::IMG;
   auto &tk = ctx().nm_ticket;  // [0] ticket, [1] operand scale, [2] number of rows left to the fix-up kernel
-  if (tk.size < 4) tk.alloc(4, true);
+  tk.reserve(4, true);
   auto &fix = ctx().nm_fix_rows;
-  if (fix.size < (size_t)lp.n_long) fix.alloc((size_t)lp.n_long);
+  fix.reserve((size_t)lp.n_long);
   LongPlanDev plan = lp.dev(C->order.data());
   auto kern = als_cg_nm_kernel<F, T>;
   auto fin = als_cg_nm_finish_kernel<F, T>;
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fin), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  allow_dynamic_lds(kern, lds);
+  allow_dynamic_lds(fin, lds);
   {
     IMP_PROF("als_cg_nm_rows");
     constexpr int forced_k = -1;  // (>= 0: a fixed operand scale 2^k instead of the one taken from the gramian's diagonal)
@@ -902,15 +900,13 @@ CholNmList least_squares_cholesky_nm(const imp_csr *C, float *X, const float *Y,
   const int32_t *b = C->bin_start;
   const size_t lds = (L::lds_floats + 128) * sizeof(float);  // + the factorisation's panel and diagonal-block buffers
   const int n_multi = C->nm_multi_rows, n_multi_seg = C->nm_multi_segs;
-  auto &ws = ctx().long_ws;
   const size_t need = (size_t)L::IMG + (size_t)n_multi_seg * (L::IMG + F);
-  if (ws.size < need) ws.alloc(need);
-  float *gram_img = ws.data(), *partial = gram_img + L::IMG;
+  float *gram_img = ctx().long_ws.reserve(need), *partial = gram_img + L::IMG;
   auto &tk = ctx().nm_ticket;  // [0] segment ticket, [1] operand scale, [2] rows left to the caller, [3] row ticket
-  if (tk.size < 4) tk.alloc(4, true);
+  tk.reserve(4, true);
   auto &fix = ctx().nm_fix_rows;
   const int capacity = C->nonempty();
-  if (fix.size < (size_t)std::max(capacity, 1)) fix.alloc((size_t)std::max(capacity, 1));
+  fix.reserve((size_t)std::max(capacity, 1));
   constexpr int forced_k = -1;
   {
     IMP_PROF("als_cholesky_nm_long");
@@ -919,8 +915,8 @@ CholNmList least_squares_cholesky_nm(const imp_csr *C, float *X, const float *Y,
       LongPlanDev plan = lp.dev(C->order.data());
       auto kern = als_cg_nm_kernel<F, float, true>;
       auto fin = als_cg_nm_finish_kernel<F, float, true>;
-      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fin), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      allow_dynamic_lds(kern, lds);
+      allow_dynamic_lds(fin, lds);
       kern<<<std::min(lp.n_seg, ctx().num_cus * 2), 256, lds, stream()>>>(plan, C->indices.data(), C->data.data(), X, Y, gram_img, -1, partial,
                                                                           tk.data(), fix.data(), 0);
       if (n_multi > 0) {
@@ -934,7 +930,7 @@ CholNmList least_squares_cholesky_nm(const imp_csr *C, float *X, const float *Y,
   if (count > 0) {
     IMP_PROF("als_cholesky_nm_rows");
     auto rk = als_chol_nm_rows_kernel<F>;
-    IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    allow_dynamic_lds(rk, lds);
     rk<<<std::min(count, ctx().num_cus * 2), 256, lds, stream()>>>(C->order.data(), b[1], count, C->indptr.data(), C->indices.data(),
                                                                     C->data.data(), X, Y, gram_img, tk.data(), fix.data());
     IMP_CHECK_HIP(hipGetLastError());

@@ -60,7 +60,7 @@ static void launch_qfteam(const imp_csr *C, int first, int count, T *X, const T 
   constexpr int WAVES = BLOCK / 64, TEAMS = WAVES / WPR;
   size_t lds = team_lds_bytes<F, WPR, BLOCK, Tile32<T>::T>();
   auto kern = als_cg_qfteam_kernel<F, WPR, BLOCK, T>;
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  allow_dynamic_lds(kern, lds);
   int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / BLOCK, (160 * 1024) / lds));
   // als_cg_q.hip launch_qteam; the 16-wave team at f = 64 (16 KB of gramian to stage, two workgroups per CU) takes 2 as well:
   // configs[1]-shaped CG 1.47 -> 1.42 ms, and a fixed share on a contended CU is what took seconds once (HISTORY.md section 6)
@@ -124,7 +124,7 @@ void launch_team_chain(const imp_csr *C, int f, const int (&first)[3], const int
       if (count[0] <= 0 && count[1] <= 0 && count[2] <= 0) return;
       const size_t lds = chain_lds_bytes<F>();
       auto kern = als_cg_qfteam_chain_kernel<F, T>;
-      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      allow_dynamic_lds(kern, lds);
       // exactly the resident workgroups: tickets do what oversubscription did (and every queue needs a workgroup)
       const int grid = std::max(ctx().num_cus * team512_per_cu(lds), ChainTickets::kQueues);
       ChainClassArgs cls;
@@ -134,8 +134,8 @@ void launch_team_chain(const imp_csr *C, int f, const int (&first)[3], const int
         cls.first[c] = first[c], cls.count[c] = std::max(count[c], 0);
       }
       Context &cx = ctx();
-      if (!cx.chain_counters.data())  // zeroed once, on the library stream
-        cx.chain_counters.alloc((size_t)ChainTickets::kClasses * ChainTickets::kQueues * ChainTickets::kCounterStride, true);
+      // zeroed once, on the library stream
+      cx.chain_counters.reserve((size_t)ChainTickets::kClasses * ChainTickets::kQueues * ChainTickets::kCounterStride, true);
       ChainTickets after = cx.chain_tickets;
       after.launch(cls.count, grid, teams, cls.base);
       IMP_PROF(name);
@@ -536,7 +536,7 @@ static void launch_qfgroup(const imp_csr *C, int first, int count, T *X, const T
   constexpr int F = 128;
   const size_t lds = QFGroupCfg<F>::lds_bytes;
   auto kern = als_cg_qfgroup_kernel<F, T>;
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  allow_dynamic_lds(kern, lds);
   int grid = std::min((count + 15) / 16, ctx().num_cus * std::max(2, ctx().oversub));  // (1 / 2 / 3 per CU measured within 1 %)
   IMP_PROF(name);
   kern<<<grid, 1024, lds, stream()>>>(C->order.data(), first, count, C->indptr.data(), C->indices.data(), C->data.data(), X, Y, A0,
@@ -599,18 +599,18 @@ void launch_wide_chain(const imp_csr *C, int f, const int (&first)[2], const int
     // the resident workgroups per CU, asked of the runtime once per process (registers and LDS allow one)
     static const int per_cu = [&] {
       int n = 0;
-      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      allow_dynamic_lds(kern, lds);
       IMP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(kern), 1024, lds));
       if (n < 1) throw std::runtime_error("launch_wide_chain: the kernel does not fit a compute unit");
       return n;
     }();
-    IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    allow_dynamic_lds(kern, lds);
     const int grid = std::max(ctx().num_cus * per_cu, WideTickets::kQueues);  // every queue needs a workgroup
     for (int c = 0; c < 2; ++c)
       if (count[c] >= WideTickets::kMaxCount) throw std::invalid_argument("launch_wide_chain: too many rows in a class");
     Context &cx = ctx();
-    if (!cx.wide_counters.data())  // zeroed once, on the library stream
-      cx.wide_counters.alloc((size_t)WideTickets::kClasses * WideTickets::kQueues * WideTickets::kCounterStride, true);
+    // zeroed once, on the library stream
+    cx.wide_counters.reserve((size_t)WideTickets::kClasses * WideTickets::kQueues * WideTickets::kCounterStride, true);
     // one launch of the classes in `on`
     auto run = [&](bool on0, bool on1) {
       WideClassArgs cls;

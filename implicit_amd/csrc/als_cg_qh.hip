@@ -109,7 +109,7 @@ static void launch_q64team(const imp_csr *C, int first, int count, ST *X, const 
   constexpr int WAVES = BLOCK / 64, TEAMS = WAVES / WPR;
   const size_t lds = team_lds_bytes<F, WPR, BLOCK, Tile64::T>();
   auto kern = als_cg_q64team_kernel<F, WPR, BLOCK, ST>;
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  allow_dynamic_lds(kern, lds);
   int per_cu = 0;  // workgroups per CU as the registers and the LDS allow
   IMP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BLOCK, lds));
   per_cu = std::max(1, per_cu);

@@ -553,7 +553,7 @@ void launch_w256_class(const imp_csr *C, int first, int count, float *X, const f
   constexpr int R = 16 / WPR;
   auto kern = als_cg_w256_kernel<WPR>;
   constexpr int lds_bytes = W256Lds<R>::bytes;
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+  allow_dynamic_lds(kern, lds_bytes);
   const int groups = (count + R - 1) / R;
   // one workgroup per CU is resident; four times as many with proportionally smaller shares even out the end of the launch
   const int grid = std::min(groups, ctx().num_cus * std::max(4, ctx().oversub));
@@ -581,11 +581,9 @@ void launch_w256_class(const imp_csr *C, int first, int count, float *X, const f
 void least_squares_cg_w256(const imp_csr *C, float *X, const float *Y, const float *A0, int cg_steps) {
   const int32_t *b = C->bin_start;
   if (b[7] - b[2] <= 0) return;
-  auto &ws = ctx().w256_ws;
   const size_t need = W256::kFragHalves / 2 + 16;  // floats: fragments (fp16) + header
-  if (ws.size < need) ws.alloc(need);
-  float *hdr = ws.data();
-  _Float16 *gfrag = reinterpret_cast<_Float16 *>(ws.data() + 16);
+  float *hdr = ctx().w256_ws.reserve(need);
+  _Float16 *gfrag = reinterpret_cast<_Float16 *>(hdr + 16);
   {
     IMP_PROF("als_cg_w256_prep");
     w256_prep_kernel<<<1, 1024, 0, stream()>>>(A0, gfrag, hdr);

@@ -717,26 +717,9 @@ __global__ __launch_bounds__(256, 3) void als_cholesky_f64_kernel(const int32_t 
   }
 }
 
-void zero_rows(const int32_t *order, int first, int count, float *X, int f);  // als_cg.hip
-
-// the device word the kernels atomicMin a failing row into, reset to "none"
-static unsigned long long *reset_failed_row() {
-  auto &failb = ctx().chol_failed;
-  if (failb.size < 1) failb.alloc(1);
-  IMP_CHECK_HIP(hipMemsetAsync(failb.data(), 0xFF, sizeof(unsigned long long), stream()));
-  return failb.data();
-}
-// waits for the sweep; -1, or the smallest failing row
-static int64_t read_failed_row(const unsigned long long *g_failed) {
-  unsigned long long failed = 0;
-  IMP_CHECK_HIP(hipMemcpyAsync(&failed, g_failed, sizeof(failed), hipMemcpyDeviceToHost, stream()));
-  sync();
-  return failed == ~0ULL ? -1 : (int64_t)failed;
-}
-
 // f = 64: every non-empty row (there is one): MFMA A-build + left-looking Cholesky, one wavefront per row
 static int64_t cholesky_f64(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg) {
-  unsigned long long *g_failed = reset_failed_row();
+  unsigned long long *g_failed = reset_fail_word();
   const int nonempty = C->nonempty();
   const size_t lds_m = ((size_t)64 * 68 + 4 * kCholTri) * sizeof(float);  // 52 KB: 3 workgroups per CU
   // 159 VGPRs, 52 KB LDS: 3 workgroups per CU resident; 8x that many are launched -- smaller fixed shares of the length-sorted
@@ -746,18 +729,15 @@ static int64_t cholesky_f64(const imp_csr *C, imp_matrix *X, const imp_matrix *Y
   LongPlanDev plan = C->plan_chol.dev(C->order.data());
   const float *partials = nullptr;
   if (plan.n_seg > 0) {
-    auto &ws = ctx().long_ws;
-    const size_t need = (size_t)plan.n_seg * kCholPartial;
-    if (ws.size < need) ws.alloc(need);
-    partials = ws.data();
+    float *ws = ctx().long_ws.reserve((size_t)plan.n_seg * kCholPartial);
+    partials = ws;
     IMP_PROF("als_cholesky_long_partials");
     const int pgrid = std::min((plan.n_seg + 3) / 4, ctx().num_cus * 8);
-    als_cholesky_f64_partial_kernel<<<pgrid, 256, 0, stream()>>>(plan, C->indices.data(), C->data.data(), Y->f32(), ws.data());
+    als_cholesky_f64_partial_kernel<<<pgrid, 256, 0, stream()>>>(plan, C->indices.data(), C->data.data(), Y->f32(), ws);
     IMP_CHECK_HIP(hipGetLastError());
   }
   {
-    IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(als_cholesky_f64_kernel<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
+    allow_dynamic_lds(als_cholesky_f64_kernel<false>, lds_m);
     IMP_PROF("als_cholesky_mfma_rows");
     als_cholesky_f64_kernel<false><<<grid, 256, lds_m, stream()>>>(C->order.data(), 0, nonempty, C->indptr.data(), C->indices.data(),
                                                                    C->data.data(), X->f32(), Y->f32(), YtY->f32(), (float)reg,
@@ -765,13 +745,13 @@ static int64_t cholesky_f64(const imp_csr *C, imp_matrix *X, const imp_matrix *Y
     IMP_CHECK_HIP(hipGetLastError());
   }
   zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), 64);
-  return read_failed_row(g_failed);
+  return read_fail_word(g_failed);
 }
 
 // any other f: the normal-matrix path at f = 128, the wave kernels for the short rows at f <= 64, the workgroup kernel for the rest
 static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg) {
   const int f = (int)X->cols;
-  unsigned long long *g_failed = reset_failed_row();
+  unsigned long long *g_failed = reset_fail_word();
   const int nonempty = C->nonempty();
   // f = 128 (round 5): the rows' normal matrices on the matrix cores, factorised on their LDS images (als_cg_nm.hip); the
   // workgroup kernel below then only takes the rows that path listed (non-positive or non-finite pivots: normally none).
@@ -800,13 +780,12 @@ static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matri
       const size_t a_words = ((size_t)m * lda + 3) & ~(size_t)3;
       const size_t lds = tiles;
       const int grid = std::min(n_block, ctx().num_cus * 2);
-      auto &ws = ctx().long_ws;
-      if (ws.size < a_words * (size_t)grid) ws.alloc(a_words * (size_t)grid);
+      float *ws = ctx().long_ws.reserve(a_words * (size_t)grid);
       IMP_PROF("als_cholesky_rows");
       auto kern = als_cholesky_blocked_kernel<false, true, 17, 16>;
-      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      allow_dynamic_lds(kern, lds);
       kern<<<grid, 256, lds, stream()>>>(C->order.data(), 0, n_block, C->indptr.data(), C->indices.data(), C->data.data(), X->f32(),
-                                         Y->f32(), YtY->f32(), f, (float)reg, lda, g_failed, 0, nullptr, ws.data());
+                                         Y->f32(), YtY->f32(), f, (float)reg, lda, g_failed, 0, nullptr, ws);
       IMP_CHECK_HIP(hipGetLastError());
     } else {
       // Packed rows of the augmented triangle (i (i + 1) / 2 + j): a must beyond f = 160, where the square image no longer fits
@@ -820,7 +799,7 @@ static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matri
       IMP_PROF("als_cholesky_rows");
       constexpr int ko = 0;  // (timing-only knock-outs of the phases: 1 A-build, 2 panel, 4 trailing update, 8 back substitution)
       auto kern = packed ? als_cholesky_blocked_kernel<true> : als_cholesky_blocked_kernel<false>;
-      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      allow_dynamic_lds(kern, lds);
       if (use_nm)  // the listed rows only (the list stands in for the schedule; a zero count makes every workgroup return at once)
         kern<<<std::min(nm_list.capacity, ctx().num_cus * per_cu), 256, lds, stream()>>>(
             reinterpret_cast<const int32_t *>(nm_list.rows), 0, nm_list.capacity, C->indptr.data(), C->indices.data(), C->data.data(),
@@ -832,7 +811,7 @@ static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matri
     }
   }
   zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), f);
-  return read_failed_row(g_failed);
+  return read_fail_word(g_failed);
 }
 
 // returns -1, or the smallest failing row

@@ -10,16 +10,6 @@
 
 namespace imp {
 
-__global__ void pad_rows_kernel(const float *__restrict__ src, float *__restrict__ dst, size_t rows, int f, int F,
-                                const int *__restrict__ skip = nullptr) {
-  if (skip && *skip) return;  // the padded copy is still the one this call needs (pad_check_kernel)
-  const size_t n = rows * (size_t)F;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / F;
-    const int c = (int)(i - r * F);
-    dst[i] = c < f ? src[r * f + c] : 0.f;
-  }
-}
 __global__ void unpad_rows_kernel(const float *__restrict__ src, float *__restrict__ dst, size_t rows, int f, int F) {
   const size_t n = rows * (size_t)f;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -52,15 +42,15 @@ PaddedViews pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *Y
   const int f = (int)X->cols;
   PaddedSystem &p = ctx().pad;
   const size_t rx = rows_of_X, ry = Y->rows;
-  if (p.x.size < rx * F) p.x.alloc(rx * F);
+  p.x.reserve(rx * F);
   // no copy is kept of memory whose writes the library does not see -- wrapped foreign memory, a matrix whose address was handed
   // out (the predicate of the cached item planes, topk.hip)
   if (!(Y->storage && Y->storage->owned && !Y->storage->exposed)) reuse_y = false;
-  // a copy that may not be re-used, or that goes with its buffer, is forgotten (before the alloc: freeing the buffer reports a
+  // a copy that may not be re-used, or that goes with its buffer, is forgotten (before the reserve: freeing the buffer reports a
   // write to that memory)
   if (!reuse_y || p.y.size < ry * F) p.forget_y();
-  if (p.y.size < ry * F) p.y.alloc(ry * F);
-  if (p.gram.size < (size_t)F * F) p.gram.alloc((size_t)F * F);
+  p.y.reserve(ry * F);
+  p.gram.reserve((size_t)F * F);
   {
     IMP_PROF("pad_factors");
     // The padded copy of Y is re-used when this call solves against the SAME matrix under the SAME gramian as the previous
@@ -71,13 +61,12 @@ PaddedViews pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *Y
     const int *skip = nullptr;
     if (ry && p.y_src == Y->data && p.y_rows == ry && p.y_f == f && p.y_F == F) {
       IMP_PROF_NESTED("padded_y_check");  // one count per call that found a kept copy to vouch for: what the cache tests read
-      if (p.same.size < 1) p.same.alloc(1);
+      skip = p.same.reserve(1);
       pad_check_kernel<<<1, 1024, 0, stream()>>>(YtY->f32(), p.gram.data(), f, F, p.same.data());
-      skip = p.same.data();
     }
-    if (ry) pad_rows_kernel<<<pad_grid(ry * F), 256, 0, stream()>>>(Y->f32(), p.y.data(), ry, f, F, skip);
+    if (ry) pad_rows(pad_grid(ry * F), Y->f32(), p.y.data(), ry, f, F, skip);
     if (reuse_y) p.y_src = Y->data, p.y_rows = ry, p.y_f = f, p.y_F = F;
-    if (rx) pad_rows_kernel<<<pad_grid(rx * F), 256, 0, stream()>>>(X->f32(), p.x.data(), rx, f, F);
+    if (rx) pad_rows(pad_grid(rx * F), X->f32(), p.x.data(), rx, f, F);
     pad_gram_kernel<<<pad_grid((size_t)F * F), 256, 0, stream()>>>(YtY->f32(), p.gram.data(), f, F);
     IMP_CHECK_HIP(hipGetLastError());
   }

@@ -29,8 +29,6 @@ namespace imp {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-void zero_rows(const int32_t *order, int first, int count, float *X, int f);  // als_cg.hip
-
 constexpr int kSubMaxF = 1024;
 constexpr int kSubPartial = 17 * 64;  // floats per segment partial: the accumulator tile in register order, then g
 
@@ -319,10 +317,8 @@ static void subspace_launch(const imp_csr *C, float *X, const float *G, const fl
   const LongPlanDev plan = C->plan_chol.dev(C->order.data());
   if (plan.n_seg > 0) {
     // [n_seg] partials, [n_long][32] deltas, [n_long] failure flags of the rows
-    auto &ws = ctx().subspace_ws;
     const size_t need = (size_t)plan.n_seg * kSubPartial + (size_t)plan.n_long * 33;
-    if (ws.size < need) ws.alloc(need);
-    float *partials = ws.data(), *delta = partials + (size_t)plan.n_seg * kSubPartial;
+    float *partials = ctx().subspace_ws.reserve(need), *delta = partials + (size_t)plan.n_seg * kSubPartial;
     int *row_failed = reinterpret_cast<int *>(delta + (size_t)plan.n_long * 32);
     IMP_CHECK_HIP(hipMemsetAsync(row_failed, 0, (size_t)plan.n_long * sizeof(int), stream()));
     const int seg_grid = (plan.n_seg + 3) / 4, row_grid = (plan.n_long + 3) / 4;
@@ -352,22 +348,15 @@ static void subspace_launch(const imp_csr *C, float *X, const float *G, const fl
 int64_t least_squares_subspace(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg, int block_size,
                                int sweeps) {
   const int f = (int)X->cols;
-  auto &failb = ctx().chol_failed;
-  if (failb.size < 1) failb.alloc(1);
-  unsigned long long *g_failed = failb.data();
-  IMP_CHECK_HIP(hipMemsetAsync(g_failed, 0xFF, sizeof(unsigned long long), stream()));
+  unsigned long long *g_failed = reset_fail_word();
   if (C->nonempty() > 0) {
-    auto &pred = ctx().subspace_pred;
-    if (pred.size < (size_t)C->nnz) pred.alloc((size_t)C->nnz);
-    if (block_size <= 8) subspace_launch<8>(C, X->f32(), YtY->f32(), Y->f32(), pred.data(), f, (float)reg, block_size, sweeps, g_failed);
-    else if (block_size <= 16) subspace_launch<16>(C, X->f32(), YtY->f32(), Y->f32(), pred.data(), f, (float)reg, block_size, sweeps, g_failed);
-    else subspace_launch<32>(C, X->f32(), YtY->f32(), Y->f32(), pred.data(), f, (float)reg, block_size, sweeps, g_failed);
+    float *pred = ctx().subspace_pred.reserve((size_t)C->nnz);
+    if (block_size <= 8) subspace_launch<8>(C, X->f32(), YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
+    else if (block_size <= 16) subspace_launch<16>(C, X->f32(), YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
+    else subspace_launch<32>(C, X->f32(), YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
   }
   zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), f);
-  unsigned long long failed = 0;
-  IMP_CHECK_HIP(hipMemcpyAsync(&failed, g_failed, sizeof(failed), hipMemcpyDeviceToHost, stream()));
-  sync();
-  return failed == ~0ULL ? -1 : (int64_t)failed;
+  return read_fail_word(g_failed);
 }
 
 }  // namespace imp

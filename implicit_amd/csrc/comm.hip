@@ -214,9 +214,7 @@ int imp_comm_ranks_seen(imp_comm *c, int *out) {
 
 int imp_comm_barrier(imp_comm *c) {
   return guarded([&] {
-    auto &word = ctx().barrier_word;
-    if (word.size < 1) word.alloc(1, true);
-    float *dummy = word.data();
+    float *dummy = ctx().barrier_word.reserve(1, true);
     IMP_CHECK_NCCL(ncclAllReduce(dummy, dummy, 1, ncclFloat, ncclSum, c->comm, stream()));
     sync();
   });

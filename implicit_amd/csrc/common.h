@@ -154,12 +154,16 @@ template <typename T> struct DeviceArray {
     storage = std::make_shared<Storage>(n * sizeof(T), zero);
     size = n;
   }
+  // grow-only workspace: a new block only when this one is shorter than n (then zeroed if asked; one that is kept is not touched)
+  T *reserve(size_t n, bool zero = false) {
+    if (size < n) alloc(n, zero);
+    return data();
+  }
   void upload(const T *host, size_t n) {
     alloc(n);
     if (n) IMP_CHECK_HIP(hipMemcpyAsync(data(), host, n * sizeof(T), hipMemcpyHostToDevice, stream()));
   }
 };
-
 // Workspaces of a zero-padded half sweep (als_pad.hip): X, Y and the gramian with F >= f columns, and which matrix `y` is a
 // padded copy of -- the chunks of a sharded CG half sweep solve against the same Y, one padded copy serves them all.
 struct PaddedSystem {
@@ -207,7 +211,7 @@ struct Context {
   DeviceArray<float> long_ws;     // partial vectors / CG state of the long rows (als_cg.hip)
   PaddedSystem pad;               // zero-padded copies for factor counts that ride the kernels of a wider one (als_pad.hip)
   DeviceArray<double> loss_buf;   // 4 accumulators of the loss kernel (solver.hip)
-  DeviceArray<unsigned long long> chol_failed;  // smallest failing row of a Cholesky sweep (als_cholesky.hip)
+  DeviceArray<unsigned long long> fail_word;    // smallest failing row / pivot of the call in flight: Cholesky and subspace sweeps, explain, spd_inverse (reset_fail_word)
   DeviceArray<float> barrier_word;              // operand of the RCCL barrier (comm.hip)
   unsigned long long *fixup_total = nullptr;     // host-mapped: rows re-solved by the fp32 fix-up kernel since the last imp_solver_fixup_rows(reset)
   DeviceArray<float> w256_ws;                    // fp16-split gramian in fragment order + header (als_cg_w256.hip)
@@ -226,6 +230,37 @@ struct Context {
   DeviceArray<float> subspace_ws;                // its long rows' segment partials, block steps and failure flags
 };
 inline hipStream_t stream() { return ctx().stream; }
+
+// ---- host-side launch conventions ----------------------------------------------
+// Dynamic LDS beyond the default limit needs the kernel's opt-in before the launch.  The attribute belongs to the kernel on
+// the CURRENT device; the call costs a microsecond or two and most launchers make it every time.
+template <typename K> void allow_dynamic_lds(K *kernel, size_t bytes) {
+  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+}
+// The same once per kernel AND DEVICE, for launches short enough for the call to weigh and kernels whose `bytes` never
+// change.  Never once per process: a process may drive several devices (imp_set_device), and the second one would launch the
+// kernel without its LDS.  The flags are only touched under a device's call lock, each device its own byte.
+template <auto Kernel> void allow_dynamic_lds_once(size_t bytes) {
+  static bool done[64] = {};
+  const int dev = ctx().device;
+  if (dev >= 0 && dev < 64 && done[dev]) return;
+  allow_dynamic_lds(Kernel, bytes);
+  if (dev >= 0 && dev < 64) done[dev] = true;
+}
+
+// The device word a sweep's kernels atomicMin their failing row (or pivot) into: ctx().fail_word, one per device.
+constexpr unsigned long long kNoFailure = ~0ULL;
+unsigned long long *reset_fail_word();                 // set to kNoFailure on the library stream (containers.hip)
+int64_t read_fail_word(const unsigned long long *w);   // waits for the stream; -1, or the smallest index recorded
+
+// containers.hip
+imp_matrix *new_matrix(size_t rows, size_t cols, size_t itemsize, bool zero);  // invalid_argument unless itemsize is 2 or 4
+std::unique_ptr<imp_matrix> astype(const imp_matrix *src, size_t itemsize);    // converted (or plain) copy, complete on return
+// dst[r][0 .. F) = src[r][0 .. f), zeros beyond; does nothing when *skip is set (pad_check_kernel, als_pad.hip).  The caller
+// chooses the grid (256 threads) and owns the profiler scope and the error check.
+template <typename T> void pad_rows(int grid, const T *src, float *dst, size_t rows, int f, int F, const int *skip = nullptr);
+// als_cg.hip
+void zero_rows(const int32_t *order, int first, int count, float *X, int f);
 // a C-ABI entry point is about to write `bytes` at `dst` through the library (or the memory is being freed): a padded copy of Y
 // made from memory it overlaps (PaddedSystem) is no longer to be trusted -- on WHICHEVER device's context the copy
 // lives (device addresses are unique across the devices of a process; a Storage may die on a thread whose current device is
@@ -361,6 +396,24 @@ CholNmList least_squares_cholesky_nm(const imp_csr *C, float *X, const float *Y,
 template <int F, typename T>
 void launch_cg_fixup(const unsigned *count, const unsigned *rows, int capacity, const imp_csr *C, T *X, const T *Y, const float *A0,
                      int cg_steps);
+
+// ---- the solver routes behind solver.hip, one block of rows each (an imp_csr without parts) ------
+// gramian.hip: out = Y^T Y + reg I
+void gramian(const float *Y, long n_rows, int f, float reg, float *out);
+void gramian_half(const void *Y, long n_rows, int f, float reg, float *out);  // fp16 rows, fp32 products
+// als_cg.hip and the kernels it dispatches to
+bool cg_native_half(int f);
+void least_squares_cg(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, int cg_steps);
+template <typename T> void least_squares_cg_q(const imp_csr *C, T *X, const T *Y, const float *A0, int f, int cg_steps);  // als_cg_q.hip
+void least_squares_cg_w256(const imp_csr *C, float *X, const float *Y, const float *A0, int cg_steps);                    // als_cg_w256.hip
+template <typename T>
+void least_squares_cg_nm(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int f, int cg_steps);  // als_cg_nm.hip
+// als_cholesky.hip, als_subspace.hip: -1, or the smallest failing row of the block
+int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg);
+int64_t least_squares_subspace(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg, int block_size,
+                               int sweeps);
+// topk.hip: the handle's max_temp_memory, for rank.hip and ease.hip, which share the handle's budget only
+size_t knn_temp_budget(const imp_knn *k);
 }  // namespace imp
 
 #endif  // IMPLICIT_AMD_CSRC_COMMON_H_

@@ -95,6 +95,18 @@ void sync_call() {
   if (!ctx().deferred) sync();
 }
 
+unsigned long long *reset_fail_word() {
+  unsigned long long *w = ctx().fail_word.reserve(1);
+  IMP_CHECK_HIP(hipMemsetAsync(w, 0xFF, sizeof(unsigned long long), stream()));  // every byte set: kNoFailure
+  return w;
+}
+int64_t read_fail_word(const unsigned long long *w) {
+  unsigned long long failed = 0;
+  IMP_CHECK_HIP(hipMemcpyAsync(&failed, w, sizeof(failed), hipMemcpyDeviceToHost, stream()));
+  sync();
+  return failed == kNoFailure ? -1 : (int64_t)failed;
+}
+
 // ---- profiler -----------------------------------------------------------------------------------
 struct ProfEntry {
   double total_ms = 0;
@@ -270,6 +282,25 @@ __global__ void cast_f16_f32_kernel(const __half *__restrict__ src, float *__res
     dst[i] = __half2float(src[i]);
 }
 
+// rows of f columns copied with F >= f, the new columns zero, fp16 converted on the way; *skip set: the copy in `dst` is still
+// the one the caller needs (pad_check_kernel, als_pad.hip)
+template <typename T>
+__global__ void pad_rows_kernel(const T *__restrict__ src, float *__restrict__ dst, size_t rows, int f, int F,
+                                const int *__restrict__ skip) {
+  if (skip && *skip) return;
+  const size_t n = rows * (size_t)F;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / F;
+    const int c = (int)(i - r * F);
+    dst[i] = c < f ? (float)src[r * f + c] : 0.f;
+  }
+}
+template <typename T> void pad_rows(int grid, const T *src, float *dst, size_t rows, int f, int F, const int *skip) {
+  pad_rows_kernel<T><<<grid, 256, 0, stream()>>>(src, dst, rows, f, F, skip);
+}
+template void pad_rows<float>(int, const float *, float *, size_t, int, int, const int *);
+template void pad_rows<__half>(int, const __half *, float *, size_t, int, int, const int *);
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -325,7 +356,7 @@ __global__ void core_clock_kernel(long long ticks, unsigned long long *out) {
   if (threadIdx.x == 0) out[0] = c1 - c0, out[1] = (unsigned long long)(w1 - w0);
 }
 
-static imp_matrix *new_matrix(size_t rows, size_t cols, size_t itemsize, bool zero) {
+imp_matrix *new_matrix(size_t rows, size_t cols, size_t itemsize, bool zero) {
   if (itemsize != 4 && itemsize != 2) throw std::invalid_argument("invalid itemsize for Matrix (must be 2 or 4)");
   auto m = std::make_unique<imp_matrix>();
   m->rows = rows;
@@ -336,14 +367,28 @@ static imp_matrix *new_matrix(size_t rows, size_t cols, size_t itemsize, bool ze
   return m.release();
 }
 
+std::unique_ptr<imp_matrix> astype(const imp_matrix *src, size_t itemsize) {
+  std::unique_ptr<imp_matrix> m(new_matrix(src->rows, src->cols, itemsize, false));
+  size_t n = src->rows * src->cols;
+  if (n) {
+    if (itemsize == src->itemsize) {
+      IMP_CHECK_HIP(hipMemcpyAsync(m->data, src->data, src->bytes(), hipMemcpyDeviceToDevice, stream()));
+    } else if (itemsize == 2) {
+      IMP_PROF("cast_f32_f16");
+      cast_f32_f16_kernel<<<grid_for(n), 256, 0, stream()>>>((const float *)src->data, (__half *)m->data, n);
+    } else {
+      IMP_PROF("cast_f16_f32");
+      cast_f16_f32_kernel<<<grid_for(n), 256, 0, stream()>>>((const __half *)src->data, (float *)m->data, n);
+    }
+    IMP_CHECK_HIP(hipGetLastError());
+  }
+  sync();
+  return m;
+}
+
 }  // namespace imp
 
 using namespace imp;
-
-// make the helper visible to the other translation units
-imp_matrix *imp_internal_new_matrix(size_t rows, size_t cols, size_t itemsize, bool zero) {
-  return new_matrix(rows, cols, itemsize, zero);
-}
 
 extern "C" {
 
@@ -734,24 +779,7 @@ int imp_matrix_assign_rows(imp_matrix *m, const imp_intvector *rowids, const imp
 }
 
 int imp_matrix_astype(const imp_matrix *src, size_t itemsize, imp_matrix **out) {
-  return guarded([&] {
-    std::unique_ptr<imp_matrix> m(new_matrix(src->rows, src->cols, itemsize, false));
-    size_t n = src->rows * src->cols;
-    if (n) {
-      if (itemsize == src->itemsize) {
-        IMP_CHECK_HIP(hipMemcpyAsync(m->data, src->data, src->bytes(), hipMemcpyDeviceToDevice, stream()));
-      } else if (itemsize == 2) {
-        IMP_PROF("cast_f32_f16");
-        cast_f32_f16_kernel<<<grid_for(n), 256, 0, stream()>>>((const float *)src->data, (__half *)m->data, n);
-      } else {
-        IMP_PROF("cast_f16_f32");
-        cast_f16_f32_kernel<<<grid_for(n), 256, 0, stream()>>>((const __half *)src->data, (float *)m->data, n);
-      }
-      IMP_CHECK_HIP(hipGetLastError());
-    }
-    sync();
-    *out = m.release();
-  });
+  return guarded([&] { *out = astype(src, itemsize).release(); });
 }
 
 int imp_matrix_calculate_norms(const imp_matrix *src, imp_matrix **out) {

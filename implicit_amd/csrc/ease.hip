@@ -23,8 +23,6 @@
 
 namespace imp {
 
-size_t knn_temp_budget(const imp_knn *k);  // topk.hip: the handle's max_temp_memory
-
 namespace {
 constexpr int kGramSlab = 16384;  // fp32 accumulators of one workgroup (64 KiB of LDS)
 constexpr int kSlabCols = 2048, kEaseBlock = 256, kEaseColsPerThread = kSlabCols / kEaseBlock;
@@ -265,12 +263,7 @@ extern "C" int imp_ease_gram(const imp_csr *item_users, const imp_csr *user_item
     if (items == 0) return;
     IMP_PROF("ease_gram");
     note_device_write(G->data, G->bytes());
-    static bool once = false;
-    if (!once) {
-      IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ease_gram_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(kGramSlab * sizeof(float))));
-      once = true;
-    }
+    allow_dynamic_lds_once<ease_gram_kernel>(kGramSlab * sizeof(float));
     const unsigned slabs = (unsigned)((items + kGramSlab - 1) / kGramSlab);
     ease_gram_kernel<<<dim3((unsigned)items, slabs), 256, kGramSlab * sizeof(float), stream()>>>(
         item_users->indptr.data(), item_users->indices.data(), item_users->data.data(), user_items->indptr.data(),

@@ -306,24 +306,18 @@ static void check_explain_args(const imp_csr *C, const imp_matrix *Y, const imp_
 int64_t explain_factor(const imp_csr *C, const imp_matrix *YtY, const imp_matrix *Y, double reg, imp_matrix *weights) {
   const int f = (int)Y->cols;
   if (C->rows == 0) return -1;
-  auto &failb = ctx().chol_failed;
-  if (failb.size < 1) failb.alloc(1);
-  IMP_CHECK_HIP(hipMemsetAsync(failb.data(), 0xFF, sizeof(unsigned long long), stream()));
+  unsigned long long *g_failed = reset_fail_word();
   const size_t lds = factor_lds_bytes(f);
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
   const int grid = std::min(C->rows, ctx().num_cus * per_cu * 4);
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(explain_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
+  allow_dynamic_lds(explain_factor_kernel, lds);
   {
     IMP_PROF("explain_factor");
     explain_factor_kernel<<<grid, 256, lds, stream()>>>(C->indptr.data(), C->indices.data(), C->data.data(), C->rows, Y->f32(),
-                                                        YtY->f32(), f, (float)reg, weights->f32(), failb.data());
+                                                        YtY->f32(), f, (float)reg, weights->f32(), g_failed);
     IMP_CHECK_HIP(hipGetLastError());
   }
-  unsigned long long failed = 0;
-  IMP_CHECK_HIP(hipMemcpyAsync(&failed, failb.data(), sizeof(failed), hipMemcpyDeviceToHost, stream()));
-  sync();
-  return failed == ~0ULL ? -1 : (int64_t)failed;
+  return read_fail_word(g_failed);
 }
 
 void explain_contributions(const imp_csr *C, const imp_matrix *Y, const imp_matrix *weights, const imp_intvector *itemids,
@@ -358,8 +352,7 @@ void explain_contributions(const imp_csr *C, const imp_matrix *Y, const imp_matr
   d_scores.alloc(pairs * (size_t)n);
   d_ids.alloc(pairs * (size_t)n);
   const size_t lds = contrib_lds_bytes(f);
-  IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(explain_contrib_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
+  allow_dynamic_lds(explain_contrib_kernel, lds);
   {
     IMP_PROF("explain_contributions");
     explain_contrib_kernel<<<grid, 256, lds, stream()>>>(C->indptr.data(), C->indices.data(), C->data.data(), Y->f32(), weights->f32(),

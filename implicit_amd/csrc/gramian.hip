@@ -323,12 +323,10 @@ template <typename T> static void gramian_t(const T *Y, long n_rows, int f, floa
   // the reference's GEMM + l2_regularize pair leaves (als.cu:122-152)
   int chunks = n_rows <= 0 ? 0 : (int)std::max<long>(1, (n_rows + rows_per_chunk - 1) / rows_per_chunk);
   size_t need = (size_t)std::max(chunks, 1) * n_pairs * 1024;
-  auto &wsbuf = ctx().gram_ws;
-  if (wsbuf.size < need) wsbuf.alloc(need);
+  float *ws = ctx().gram_ws.reserve(need);
   if (chunks > 0) {
     IMP_PROF("gramian_partial");
     dim3 grid(chunks, gy, 1);
-    float *ws = wsbuf.data();
     if (vw == 4) gramian_partial_vec_kernel<4, T><<<grid, 256, 0, stream()>>>(Y, n_rows, rows_per_chunk, ws);
     else if (vw == 2) gramian_partial_vec_kernel<2, T><<<grid, 256, 0, stream()>>>(Y, n_rows, rows_per_chunk, ws);
     else if (tpw == 1) gramian_partial_kernel<1, T><<<grid, 256, 0, stream()>>>(Y, n_rows, f, rows_per_chunk, ws);
@@ -338,7 +336,7 @@ template <typename T> static void gramian_t(const T *Y, long n_rows, int f, floa
   }
   {
     IMP_PROF("gramian_reduce");
-    gramian_reduce_kernel<<<n_pairs * 16, 1024, 0, stream()>>>(wsbuf.data(), chunks, f, reg, out, vw);
+    gramian_reduce_kernel<<<n_pairs * 16, 1024, 0, stream()>>>(ws, chunks, f, reg, out, vw);
     IMP_CHECK_HIP(hipGetLastError());
   }
 }

@@ -70,16 +70,7 @@ constexpr int64_t kIvfMaxCounters = (int64_t)1 << 24;  // runs x keys of the gro
 __device__ __forceinline__ uint64_t ivf_max64(uint64_t a, uint64_t b) { return a < b ? b : a; }
 __device__ __forceinline__ int64_t ivf_min64(int64_t a, int64_t b) { return a < b ? a : b; }
 
-// ---- padding, centroids ------------------------------------------------------------------------------------------------
-template <typename T> __global__ void ivf_pad_kernel(const T *__restrict__ src, size_t rows, int f, int f_pad, float *__restrict__ dst) {
-  const size_t total = rows * (size_t)f_pad;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / f_pad;
-    const int d = (int)(i - r * f_pad);
-    dst[i] = d < f ? (float)src[r * f + d] : 0.f;
-  }
-}
-
+// ---- centroids (the padded copies are pad_rows', common.h) ---------------------------------------------------------------
 // sum of squares of row[0 .. f_pad) over the 256 threads of a workgroup, in a fixed tree; `red` holds 256 floats
 __device__ float ivf_block_sumsq(const float *row, int f_pad, float *red) {
   float s = 0.f;
@@ -518,18 +509,12 @@ static void ivf_pad(const void *src, size_t itemsize, size_t rows, int f, int f_
   if (!rows) return;
   IMP_PROF("ivf_pad");
   const int grid = ivf_grid(rows * f_pad, 256);
-  if (itemsize == 4)
-    hipLaunchKernelGGL(ivf_pad_kernel<float>, dim3(grid), dim3(256), 0, stream(), static_cast<const float *>(src), rows, f, f_pad, dst);
-  else
-    hipLaunchKernelGGL(ivf_pad_kernel<__half>, dim3(grid), dim3(256), 0, stream(), static_cast<const __half *>(src), rows, f, f_pad, dst);
+  if (itemsize == 4) pad_rows(grid, static_cast<const float *>(src), dst, rows, f, f_pad);
+  else pad_rows(grid, static_cast<const __half *>(src), dst, rows, f, f_pad);
   IMP_CHECK_HIP(hipGetLastError());
 }
 
 // scratch of one grouping of at most n_max elements by nkeys keys
-template <typename T> static void ivf_ensure(DeviceArray<T> &a, size_t n) {
-  if (a.size < n) a.alloc(n);
-}
-
 struct IvfGrouper {
   int nkeys = 0, nruns = 0;
   int64_t n_max = 0;
@@ -537,7 +522,7 @@ struct IvfGrouper {
   DeviceArray<int32_t> totals;
   IvfGrouper(int64_t n_max_, int nkeys_, DeviceArray<unsigned> &cnt_) : nkeys(nkeys_), n_max(n_max_), cnt(cnt_) {
     nruns = (int)std::max<int64_t>(1, std::min<int64_t>((n_max + kIvfRun - 1) / kIvfRun, kIvfMaxCounters / nkeys));
-    ivf_ensure(cnt, (size_t)nruns * nkeys);
+    cnt.reserve((size_t)nruns * nkeys);
     totals.alloc(nkeys);
   }
   // off[nkeys + 1], order[n]: the elements by (key, element index); inv[n] (nullable): an element's place in `order`
@@ -710,9 +695,9 @@ extern "C" int imp_ivf_search(imp_ivf *ix, const imp_matrix *query, int k, int n
     imp_ivf::Workspace &ws = ix->ws;
     DeviceArray<float> &Q = ws.Q, &S = ws.S, &probe_dist = ws.probe_dist, &out_dist = ws.out_dist;
     DeviceArray<int32_t> &d_probes = ws.probes, &sorted = ws.sorted, &inv = ws.inv, &pair_off = ws.pair_off, &out_ids = ws.out_ids;
-    ivf_ensure(Q, chunk * f_pad), ivf_ensure(S, chunk * max_cand), ivf_ensure(probe_dist, chunk * P), ivf_ensure(out_dist, chunk * k);
-    ivf_ensure(d_probes, chunk * P), ivf_ensure(sorted, chunk * P), ivf_ensure(inv, chunk * P), ivf_ensure(pair_off, (size_t)nlist + 1);
-    ivf_ensure(out_ids, chunk * k);
+    Q.reserve(chunk * f_pad), S.reserve(chunk * max_cand), probe_dist.reserve(chunk * P), out_dist.reserve(chunk * k);
+    d_probes.reserve(chunk * P), sorted.reserve(chunk * P), inv.reserve(chunk * P), pair_off.reserve((size_t)nlist + 1);
+    out_ids.reserve(chunk * k);
     IvfProduct coarse(1), scan(nlist);
     IvfGrouper grouper((int64_t)(chunk * P), nlist, ws.group_cnt);
     int ppad = 1;

@@ -255,9 +255,7 @@ extern "C" int imp_lmf_update(const imp_csr *cui, imp_matrix *X, const imp_matri
                 nullptr, lp.dev(cui->order.data()), cui->nnz, cui->bin_start[1], cui->bin_start[imp_csr::kBins - 1], (uint64_t)seed,
                 learning_rate, regularization, C, neg_prop};
       if (lp.n_seg > 0) {
-        auto &ws = ctx().lmf_ws;
-        if (ws.size < (size_t)lp.n_seg * C) ws.alloc((size_t)lp.n_seg * C);
-        a.ws = ws.data();
+        a.ws = ctx().lmf_ws.reserve((size_t)lp.n_seg * C);
         IMP_PROF("lmf_segments");
         launch_lmf(a, kLmfSegments, lp.n_seg);
       }

@@ -83,9 +83,7 @@ void pair_update(const char *who, const char *check_prof, const char *prof, cons
   *count0 = *count1 = 0;
   if (nnz == 0 || n == 0) return;
 
-  auto &st = ctx().pair_stats;
-  if (st.size < 3) st.alloc(3);
-  unsigned long long *stats = st.data();
+  unsigned long long *stats = ctx().pair_stats.reserve(3);
   IMP_CHECK_HIP(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), stream()));
   check_pair_ids(who, check_prof, userids, itemids, indptr, X->rows, Y->rows, stats + 2);
 

@@ -46,8 +46,6 @@ __global__ void normal_kernel(float *__restrict__ out, size_t n, uint64_t seed, 
 
 using namespace imp;
 
-imp_matrix *imp_internal_new_matrix(size_t rows, size_t cols, size_t itemsize, bool zero);
-
 struct imp_random {
   uint64_t seed = 42;
   uint32_t draws = 0;
@@ -69,7 +67,7 @@ int imp_random_destroy(imp_random *r) {
 
 int imp_random_uniform(imp_random *r, size_t rows, size_t cols, float low, float high, imp_matrix **out) {
   return guarded([&] {
-    std::unique_ptr<imp_matrix> m(imp_internal_new_matrix(rows, cols, 4, false));
+    std::unique_ptr<imp_matrix> m(new_matrix(rows, cols, 4, false));
     size_t n = rows * cols;
     if (n) {
       IMP_PROF("rng_uniform");
@@ -84,7 +82,7 @@ int imp_random_uniform(imp_random *r, size_t rows, size_t cols, float low, float
 
 int imp_random_randn(imp_random *r, size_t rows, size_t cols, float mean, float stddev, imp_matrix **out) {
   return guarded([&] {
-    std::unique_ptr<imp_matrix> m(imp_internal_new_matrix(rows, cols, 4, false));
+    std::unique_ptr<imp_matrix> m(new_matrix(rows, cols, 4, false));
     size_t n = rows * cols;
     if (n) {
       IMP_PROF("rng_normal");

@@ -26,8 +26,6 @@
 
 namespace imp {
 
-size_t knn_temp_budget(const imp_knn *k);  // topk.hip: the handle's max_temp_memory
-
 constexpr int kRankBlock = 512;
 constexpr int kRankWaves = kRankBlock / 64;
 constexpr int kRankUnroll = 4;        // candidate rows a wavefront has in flight

@@ -9,14 +9,6 @@
 
 namespace imp {
 
-void gramian(const float *Y, long n_rows, int f, float reg, float *out);                                    // gramian.hip
-void gramian_half(const void *Y, long n_rows, int f, float reg, float *out);                               // fp16 rows, fp32 products
-bool cg_native_half(int f);                                                                                 // als_cg.hip
-void least_squares_cg(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, int cg_steps);  // als_cg.hip
-int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg);
-int64_t least_squares_subspace(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg, int block_size,
-                               int sweeps);  // als_subspace.hip
-
 // K7: loss numerator terms, one wavefront per user row (oracle: implicit/cpu/_als.pyx:257-308):
 //   r = YtY x + sum_k ((c>0 ? -2c : 0) + (|c|-1) y.x) y ;  loss += r.x + sum |c| ; user_norm += x.x
 // fp64 accumulation as in the oracle (:272); per-wave partials are added with fp64 atomics.
@@ -105,13 +97,23 @@ template <typename Fn> static void for_each_part(const imp_csr *C, const imp_mat
     fn(C->parts[i].get(), &view);
   }
 }
+// solve(block, rows of X) returns -1 or the block's smallest failing row, and is run on every block whatever the others return;
+// the first failing row of the whole matrix, or -1
+template <typename Fn> static int64_t first_failed_row(const imp_csr *C, imp_matrix *X, Fn &&solve) {
+  int64_t failed = -1;
+  size_t block = 0;
+  for_each_part(C, X, [&](const imp_csr *part, const imp_matrix *xp) {
+    const int64_t bad = solve(part, const_cast<imp_matrix *>(xp));
+    if (bad >= 0 && failed < 0) failed = bad + (C->parts.empty() ? 0 : C->part_row0[block]);
+    ++block;
+  });
+  return failed;
+}
 
 float calculate_loss(const imp_csr *C, const imp_matrix *X, const imp_matrix *Y, float reg) {
   const int f = (int)X->cols;
   if (f > 1024) throw std::invalid_argument("calculate_loss: factors must be <= 1024 (as the reference, implicit/gpu/als.cu:262-264)");
-  auto &lossb = ctx().loss_buf;
-  if (lossb.size < 4) lossb.alloc(4);
-  double *g_loss_buf = lossb.data();
+  double *g_loss_buf = ctx().loss_buf.reserve(4);
   IMP_CHECK_HIP(hipMemsetAsync(g_loss_buf, 0, 4 * sizeof(double), stream()));
   DeviceArray<float> yty;
   yty.alloc((size_t)f * f);
@@ -162,8 +164,6 @@ static void check_solver_args(const imp_csr *C, const imp_matrix *X, const imp_m
 
 using namespace imp;
 
-extern "C" int imp_matrix_astype(const imp_matrix *src, size_t itemsize, imp_matrix **out);
-
 struct imp_solver {
   int dummy = 0;
 };
@@ -199,14 +199,9 @@ static void run_with_f32(const imp_csr *cui, imp_matrix *X, const imp_matrix *Y,
     return;
   }
   // fp16 storage: up-convert, solve in fp32, down-convert X back in place
-  imp_matrix *x32 = nullptr, *y32 = nullptr, *x16 = nullptr;
-  if (imp_matrix_astype(X, 4, &x32) != IMP_OK) throw std::runtime_error(imp_last_error());
-  std::unique_ptr<imp_matrix> gx(x32);
-  if (imp_matrix_astype(Y, 4, &y32) != IMP_OK) throw std::runtime_error(imp_last_error());
-  std::unique_ptr<imp_matrix> gy(y32);
-  body(x32, y32);
-  if (imp_matrix_astype(x32, 2, &x16) != IMP_OK) throw std::runtime_error(imp_last_error());
-  std::unique_ptr<imp_matrix> g16(x16);
+  const auto x32 = astype(X, 4), y32 = astype(Y, 4);
+  body(x32.get(), y32.get());
+  const auto x16 = astype(x32.get(), 2);
   IMP_CHECK_HIP(hipMemcpyAsync(X->data, x16->data, X->bytes(), hipMemcpyDeviceToDevice, stream()));
   sync();
 }
@@ -240,11 +235,8 @@ int imp_solver_least_squares_cholesky(imp_solver *, const imp_csr *cui, imp_matr
     note_device_write(X->data, X->bytes());  // the rows this call solves
     int64_t failed = -1;
     run_with_f32(cui, X, Y, [&](imp_matrix *x, const imp_matrix *y) {
-      size_t block = 0;
-      for_each_part(cui, x, [&](const imp_csr *part, const imp_matrix *xp) {
-        const int64_t bad = least_squares_cholesky(part, const_cast<imp_matrix *>(xp), YtY, y, regularization);
-        if (bad >= 0 && failed < 0) failed = bad + (cui->parts.empty() ? 0 : cui->part_row0[block]);
-        ++block;
+      failed = first_failed_row(cui, x, [&](const imp_csr *part, imp_matrix *xp) {
+        return least_squares_cholesky(part, xp, YtY, y, regularization);
       });
     });
     if (failed_row) *failed_row = failed;
@@ -264,12 +256,8 @@ int imp_solver_least_squares_subspace(imp_solver *, const imp_csr *cui, imp_matr
     if (block_size < 1 || block_size > 32) throw std::invalid_argument("least_squares_subspace: block_size must be 1 .. 32");
     if (sweeps < 1) throw std::invalid_argument("least_squares_subspace: sweeps must be >= 1");
     note_device_write(X->data, (size_t)cui->rows * X->cols * X->itemsize);  // the rows this call solves
-    int64_t failed = -1;
-    size_t block = 0;
-    for_each_part(cui, X, [&](const imp_csr *part, const imp_matrix *xp) {
-      const int64_t bad = least_squares_subspace(part, const_cast<imp_matrix *>(xp), YtY, Y, regularization, block_size, sweeps);
-      if (bad >= 0 && failed < 0) failed = bad + (cui->parts.empty() ? 0 : cui->part_row0[block]);
-      ++block;
+    const int64_t failed = first_failed_row(cui, X, [&](const imp_csr *part, imp_matrix *xp) {
+      return least_squares_subspace(part, xp, YtY, Y, regularization, block_size, sweeps);
     });
     if (failed_row) *failed_row = failed;
     if (failed >= 0)
@@ -287,12 +275,8 @@ int imp_solver_calculate_loss(imp_solver *, const imp_csr *cui, const imp_matrix
     if (X->itemsize == 4 && Y->itemsize == 4) {
       *loss_out = calculate_loss(cui, X, Y, regularization);
     } else {
-      imp_matrix *x32 = nullptr, *y32 = nullptr;
-      if (imp_matrix_astype(X, 4, &x32) != IMP_OK) throw std::runtime_error(imp_last_error());
-      std::unique_ptr<imp_matrix> gx(x32);
-      if (imp_matrix_astype(Y, 4, &y32) != IMP_OK) throw std::runtime_error(imp_last_error());
-      std::unique_ptr<imp_matrix> gy(y32);
-      *loss_out = calculate_loss(cui, x32, y32, regularization);
+      const auto x32 = astype(X, 4), y32 = astype(Y, 4);
+      *loss_out = calculate_loss(cui, x32.get(), y32.get(), regularization);
     }
   });
 }

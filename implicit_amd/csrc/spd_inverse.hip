@@ -31,7 +31,6 @@ namespace imp {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
-constexpr unsigned long long kNoPivot = ~0ULL;
 constexpr int kGemmTile = 128, kGemmK = 16, kGemmLd = kGemmK + 1;
 constexpr int kSpdBlock = 128;  // at most kGemmTile: the in-place panel product relies on one column of tiles
 
@@ -53,7 +52,7 @@ struct GemmArgs {
 
 __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs g) {
   __shared__ float As[kGemmTile * kGemmLd], Bs[kGemmTile * kGemmLd];
-  if (*g.failed != kNoPivot) return;
+  if (*g.failed != kNoFailure) return;
   const int row0 = blockIdx.y * kGemmTile, col0 = blockIdx.x * kGemmTile;
   if (g.lower_only && col0 > row0) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(256) void spd_diag_kernel(float *A, long n, int k0,
   extern __shared__ float spd_lds[];
   constexpr int LD = NB + 1;
   float *L = spd_lds, *W = spd_lds + NB * LD;
-  if (*failed != kNoPivot) return;
+  if (*failed != kNoFailure) return;
   __shared__ float col[NB];
   __shared__ float pivot;
   const int tid = threadIdx.x;
@@ -296,11 +295,7 @@ void launch_gemm(const GemmArgs &g) {
 
 template <int NB> void launch_diag(float *A, long n, int k0, float *Wd, float *V, unsigned long long *failed) {
   constexpr size_t lds = 2 * (size_t)NB * (NB + 1) * sizeof(float);
-  static bool once = false;
-  if (!once) {
-    IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(spd_diag_kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    once = true;
-  }
+  allow_dynamic_lds_once<spd_diag_kernel<NB>>(lds);
   spd_diag_kernel<NB><<<1, 256, lds, stream()>>>(A, n, k0, Wd, V, failed);
   IMP_CHECK_HIP(hipGetLastError());
 }
@@ -328,10 +323,7 @@ static int64_t spd_inverse(float *A, size_t n_) {
                              std::to_string(n) + " (" + e.what() + ")");
   }
   float *V = ws.data(), *Wd = V + (size_t)n * n;
-  auto &failb = ctx().chol_failed;
-  if (failb.size < 1) failb.alloc(1);
-  unsigned long long *failed = failb.data();
-  IMP_CHECK_HIP(hipMemsetAsync(failed, 0xFF, sizeof(unsigned long long), stream()));
+  unsigned long long *failed = reset_fail_word();
   IMP_CHECK_HIP(hipMemsetAsync(V, 0, (size_t)n * n * sizeof(float), stream()));
   {
     IMP_PROF_NESTED("spd_inverse_factor");
@@ -364,10 +356,7 @@ static int64_t spd_inverse(float *A, size_t n_) {
     launch_gemm(GemmArgs{V, n, (int)n, V, n, (int)n, A, n, 0, (int)n, 1, 1, 1.f, 0.f, failed});
     mirror_lower(A, (size_t)n);
   }
-  unsigned long long f = 0;
-  IMP_CHECK_HIP(hipMemcpyAsync(&f, failed, sizeof(f), hipMemcpyDeviceToHost, stream()));
-  sync();
-  return f == kNoPivot ? -1 : (int64_t)f;
+  return read_fail_word(failed);
 }
 
 }  // namespace imp

@@ -574,18 +574,6 @@ __global__ void item_bitmap_kernel(uint32_t *__restrict__ bits, int ni, const in
   }
 }
 
-// factor counts that are not a multiple of 16 (the reference's CPU default is 100): rows zero-padded to the next multiple, fp16
-// converted on the way -- extra zero factors change no dot product, and the scores come from the direct-operand kernels
-template <typename T>
-__global__ void pad_factor_rows_kernel(const T *__restrict__ src, float *__restrict__ dst, size_t rows, int f, int F) {
-  const size_t n = rows * (size_t)F;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / F;
-    const int c = (int)(i - r * F);
-    dst[i] = c < f ? load1(src + r * f + c) : 0.f;
-  }
-}
-
 // fallback rows: query rows gathered into a compact matrix, filters replayed from the bitmaps onto the materialised scores
 template <typename TQ>
 __global__ void gather_query_rows_kernel(const TQ *__restrict__ Q, const int32_t *__restrict__ rows, int n, int f,
@@ -646,8 +634,6 @@ static bool is_host_pointer(const void *p) {
 }  // namespace imp
 
 using namespace imp;
-
-extern "C" int imp_matrix_astype(const imp_matrix *src, size_t itemsize, imp_matrix **out);
 
 struct imp_knn {
   size_t max_temp_memory = 0;
@@ -710,14 +696,10 @@ struct imp_knn {
       if (p) (void)hipHostFree(p);
     }
   } host_stage;
-  template <typename T> static T *ensure(DeviceArray<T> &a, size_t n) {
-    if (a.size < n) a.alloc(n);
-    return a.data();
-  }
 };
 
 namespace imp {
-size_t knn_temp_budget(const imp_knn *k) { return k->max_temp_memory; }  // for rank.hip, which shares the handle's budget only
+size_t knn_temp_budget(const imp_knn *k) { return k->max_temp_memory; }
 }
 
 // ---- host side of imp_knn_topk: checks -> operands -> outputs -> (emit | materialise) -> deliver ----------------------------
@@ -774,7 +756,7 @@ template <typename T> static T *place_output(const OutputStage &o, const T *call
     if (preset) std::copy(caller, caller + o.out_words, stage);
     return stage;
   }
-  T *d = imp_knn::ensure(dev, o.out_words);
+  T *d = dev.reserve(o.out_words);
   if (preset) IMP_CHECK_HIP(hipMemcpyAsync(d, caller, o.out_words * 4, hipMemcpyHostToDevice, stream()));
   return d;
 }
@@ -812,24 +794,23 @@ struct TopkOperands {
   bool half;                                           // both are fp16 as stored
   std::unique_ptr<imp_matrix> items_conv, query_conv;  // the converted copies live as long as the call
 };
+// factor counts that are not a multiple of 16 (the reference's CPU default is 100): rows zero-padded to the next multiple, fp16
+// converted on the way -- extra zero factors change no dot product, and the scores come from the direct-operand kernels
 template <typename T> static void pad_factors(const imp_matrix *m, float *out, int f) {
-  pad_factor_rows_kernel<T><<<std::max(1, grid_1d(m->rows * (size_t)f, 16)), 256, 0, stream()>>>(static_cast<const T *>(m->data), out, m->rows, (int)m->cols, f);
+  pad_rows(std::max(1, grid_1d(m->rows * (size_t)f, 16)), static_cast<const T *>(m->data), out, m->rows, (int)m->cols, f);
 }
 static TopkOperands prepare_operands(imp_knn *knn, const imp_matrix *items_in, const imp_matrix *query_in, int f, bool fast) {
   TopkOperands op{items_in->data, query_in->data, items_in->itemsize == 2, nullptr, nullptr};
   if (f != (int)items_in->cols) {
-    float *pi = imp_knn::ensure(knn->pad_items, items_in->rows * (size_t)f), *pq = imp_knn::ensure(knn->pad_query, query_in->rows * (size_t)f);
+    float *pi = knn->pad_items.reserve(items_in->rows * (size_t)f), *pq = knn->pad_query.reserve(query_in->rows * (size_t)f);
     IMP_PROF("pad_factors");
     if (op.half) pad_factors<__half>(items_in, pi, f), pad_factors<__half>(query_in, pq, f);
     else pad_factors<float>(items_in, pi, f), pad_factors<float>(query_in, pq, f);
     IMP_CHECK_HIP(hipGetLastError());
     op.items = pi, op.query = pq, op.half = false;
   } else if (op.half && !fast) {
-    imp_matrix *t = nullptr;
-    if (imp_matrix_astype(items_in, 4, &t) != IMP_OK) throw std::runtime_error(imp_last_error());
-    op.items_conv.reset(t);
-    if (imp_matrix_astype(query_in, 4, &t) != IMP_OK) throw std::runtime_error(imp_last_error());
-    op.query_conv.reset(t);
+    op.items_conv = astype(items_in, 4);
+    op.query_conv = astype(query_in, 4);
     op.items = op.items_conv->data, op.query = op.query_conv->data, op.half = false;
   }
   return op;
@@ -849,9 +830,7 @@ template <typename TQ, typename TI> static ResidentArgs split_planes(const TopkC
   if (!same) {
     IMP_PROF_NESTED("item_planes_split");  // one count per (re)build of the item planes: what the cache tests read
     ip.key.src = nullptr;
-    if (ip.planes.size < ni_pad * F * 2) ip.planes.alloc(ni_pad * F * 2);
-    if (ip.exp.size < 1) ip.exp.alloc(1), ip.maxbits.alloc(1), ip.ne.alloc(4);
-    if (ip.tile_n.size < ni_pad / 32) ip.tile_n.alloc(ni_pad / 32);
+    ip.planes.reserve(ni_pad * F * 2), ip.exp.reserve(1), ip.maxbits.reserve(1), ip.ne.reserve(4), ip.tile_n.reserve(ni_pad / 32);
     IMP_CHECK_HIP(hipMemsetAsync(ip.maxbits.data(), 0, sizeof(unsigned), stream()));
     IMP_CHECK_HIP(hipMemsetAsync(ip.ne.data(), 0, 4 * sizeof(unsigned), stream()));
     IMP_CHECK_HIP(hipMemsetAsync(ip.tile_n.data(), 0, (ni_pad / 32) * sizeof(unsigned), stream()));
@@ -864,9 +843,9 @@ template <typename TQ, typename TI> static ResidentArgs split_planes(const TopkC
     if (trusted) ip.key.src = items_in->data, ip.key.bytes = items_in->bytes();
   }
   const size_t nq_pad = rq_query_pad(nq);
-  _Float16 *qp = imp_knn::ensure(c.knn->query_planes, nq_pad * F * 2);
-  int *qe = imp_knn::ensure(c.knn->query_exp, nq_pad);
-  float *qerr = imp_knn::ensure(c.knn->query_err, 2 * nq_pad);
+  _Float16 *qp = c.knn->query_planes.reserve(nq_pad * F * 2);
+  int *qe = c.knn->query_exp.reserve(nq_pad);
+  float *qerr = c.knn->query_err.reserve(2 * nq_pad);
   rq_split_queries_kernel<TQ><<<(int)std::min<size_t>((nq_pad + 3) / 4, (size_t)ctx().num_cus * 8), 256, 0, stream()>>>(Qb, qp, qe, nq, nq_pad, f, KS,
                                                                                                                        qerr, qerr + nq_pad);
   IMP_CHECK_HIP(hipGetLastError());
@@ -888,7 +867,7 @@ static void launch_select_exact(const TopkCall &c, bool set_lds, const float *sc
   const size_t lds = c.use_lds ? (size_t)c.kpad * 8 : 0;
   auto kern = select_kernel<512>;
   if (set_lds)
-    IMP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(lds, 1)));
+    allow_dynamic_lds(kern, std::max<size_t>(lds, 1));
   kern<<<(unsigned)rows, 512, lds, stream()>>>(scores, (int)c.ni, c.k_eff, c.kpad, ids, dist, c.k, gcand, c.use_lds ? 1 : 0, flagged);
   IMP_CHECK_HIP(hipGetLastError());
 }
@@ -935,14 +914,14 @@ static void emit_fallback_rows(const TopkCall &c, const TQ *qptr, const TI *Ib, 
   constexpr int FB = 64;  // fallback rows per materialised group
   imp_knn *knn = c.knn;
   const int ni = (int)c.ni, f = c.f, k = c.k, n_tiles = c.n_tiles;
-  int32_t *d_rows = imp_knn::ensure(knn->fb_rows, fb_list.size());
+  int32_t *d_rows = knn->fb_rows.reserve(fb_list.size());
   IMP_CHECK_HIP(hipMemcpyAsync(d_rows, fb_list.data(), fb_list.size() * 4, hipMemcpyHostToDevice, stream()));
-  float *fbq = imp_knn::ensure(knn->fb_query, (size_t)FB * f);
-  float *fscores = imp_knn::ensure(knn->scores, (size_t)FB * c.ni);
-  float *ftile = imp_knn::ensure(knn->tile_max, (size_t)FB * n_tiles);
-  int32_t *fids = imp_knn::ensure(knn->fb_ids, (size_t)FB * k);
-  float *fdist = imp_knn::ensure(knn->fb_dist, (size_t)FB * k);
-  uint64_t *fg = c.use_lds ? nullptr : imp_knn::ensure(knn->gcand, (size_t)FB * c.kpad);
+  float *fbq = knn->fb_query.reserve((size_t)FB * f);
+  float *fscores = knn->scores.reserve((size_t)FB * c.ni);
+  float *ftile = knn->tile_max.reserve((size_t)FB * n_tiles);
+  int32_t *fids = knn->fb_ids.reserve((size_t)FB * k);
+  float *fdist = knn->fb_dist.reserve((size_t)FB * k);
+  uint64_t *fg = c.use_lds ? nullptr : knn->gcand.reserve((size_t)FB * c.kpad);
   for (size_t g0 = 0; g0 < fb_list.size(); g0 += FB) {
     const int n = (int)std::min<size_t>(FB, fb_list.size() - g0);
     gather_query_rows_kernel<TQ><<<std::max(1, (n * f + 255) / 256), 256, 0, stream()>>>(qptr, d_rows + g0, n, f, fbq);
@@ -966,15 +945,15 @@ template <typename TQ, typename TI, bool BF3> static void emit_route(const TopkC
   const imp_coo *qf = c.query_filter;
   const imp_intvector *itf = c.item_filter;
   const int words = (int)((c.ni + 31) / 32), n_blocks = (int)((c.ni + 127) / 128), n_sub = (n_blocks + stride - 1) / stride, sub_cols = n_sub * 128;
-  float *sub = imp_knn::ensure(knn->sub_scores, ebatch * (size_t)sub_cols);
-  uint32_t *tau = imp_knn::ensure(knn->tau, (ebatch + 127) / 128 * 128);  // the emit epilogue loads thresholds four rows at a time
-  unsigned int *cnt = imp_knn::ensure(knn->cand_count, ebatch);
-  uint64_t *cand = imp_knn::ensure(knn->cand, ebatch * (size_t)kEmitCap);
-  float *row_unscale = imp_knn::ensure(knn->row_unscale, rq_query_pad(ebatch));
+  float *sub = knn->sub_scores.reserve(ebatch * (size_t)sub_cols);
+  uint32_t *tau = knn->tau.reserve((ebatch + 127) / 128 * 128);  // the emit epilogue loads thresholds four rows at a time
+  unsigned int *cnt = knn->cand_count.reserve(ebatch);
+  uint64_t *cand = knn->cand.reserve(ebatch * (size_t)kEmitCap);
+  float *row_unscale = knn->row_unscale.reserve(rq_query_pad(ebatch));
   int *flags = c.out.host_flags, *list_len = c.out.host_counts;
-  if (qf && knn->row_bits.size < ebatch * (size_t)words) knn->row_bits_dirty = true;  // (regrown: fresh memory)
-  uint32_t *row_bits = qf ? imp_knn::ensure(knn->row_bits, ebatch * (size_t)words) : nullptr;
-  uint32_t *item_bits = itf ? imp_knn::ensure(knn->item_bits, (size_t)words) : nullptr;
+  if (qf && knn->row_bits.size < ebatch * (size_t)words) knn->row_bits_dirty = true;  // (about to be regrown: fresh memory)
+  uint32_t *row_bits = qf ? knn->row_bits.reserve(ebatch * (size_t)words) : nullptr;
+  uint32_t *item_bits = itf ? knn->item_bits.reserve((size_t)words) : nullptr;
   if (itf) IMP_CHECK_HIP(hipMemsetAsync(item_bits, 0, (size_t)words * 4, stream()));
   // fp16 two-term form with the queries resident in registers and the item planes cached (topk_resident.h): every factor count
   // that pads to 32 / 64 / 128 / 256; fp16-stored factors too (their values are their own high halves: scores stay bit-identical
@@ -988,7 +967,7 @@ template <typename TQ, typename TI, bool BF3> static void emit_route(const TopkC
   } else if (BF3) {
     IMP_PROF("split_query_rows");
     const size_t nq_pad = (nq + 127) / 128 * 128;  // whole 128-row query blocks: a workgroup reads all four tiles of its block
-    qs = imp_knn::ensure(knn->query_split, nq_pad * 3 * (size_t)f);
+    qs = knn->query_split.reserve(nq_pad * 3 * (size_t)f);
     split_query_rows_kernel<TQ><<<std::max(1, grid_1d(nq_pad * (size_t)f, 16)), 256, 0, stream()>>>(Qb, reinterpret_cast<__bf16 *>(qs), nq, nq_pad, f);
     IMP_CHECK_HIP(hipGetLastError());
   }
@@ -997,7 +976,7 @@ template <typename TQ, typename TI, bool BF3> static void emit_route(const TopkC
   // screened emit pass (topk_resident.h MODE 3): one-product scores against tau - eps, the few candidates that can still be among
   // the best k re-scored in fp32 by the select kernel.  Dot-product scores only (no item norms); IMP_TOPK_SCREEN=0: three products
   const bool screen = resident && sw.screen && !c.norms;
-  float *row_eps = screen ? imp_knn::ensure(knn->row_eps, rq_query_pad(ebatch)) : nullptr;
+  float *row_eps = screen ? knn->row_eps.reserve(rq_query_pad(ebatch)) : nullptr;
   std::vector<int32_t> fb_list;
   for (size_t start = 0; start < nq; start += ebatch) {
     const size_t end = std::min(nq, start + ebatch), rows = end - start;
@@ -1108,10 +1087,10 @@ template <typename TQ, typename TI, bool BF3> static void materialise_route(cons
   const int KS = rq_ks_for(f);
   const bool resident = BF3 && fast && topk_switches().resident && KS > 0 && (batch == nq || batch >= 128);
   if (resident && batch < nq) batch = batch / 128 * 128;
-  float *scores = imp_knn::ensure(knn->scores, batch * c.ni);
-  uint64_t *gcand = c.use_lds ? nullptr : imp_knn::ensure(knn->gcand, batch * (size_t)c.kpad);
-  float *tile_max = fast ? imp_knn::ensure(knn->tile_max, batch * (size_t)n_tiles) : nullptr;
-  int *fallback = fast ? imp_knn::ensure(knn->fallback, batch) : nullptr;
+  float *scores = knn->scores.reserve(batch * c.ni);
+  uint64_t *gcand = c.use_lds ? nullptr : knn->gcand.reserve(batch * (size_t)c.kpad);
+  float *tile_max = fast ? knn->tile_max.reserve(batch * (size_t)n_tiles) : nullptr;
+  int *fallback = fast ? knn->fallback.reserve(batch) : nullptr;
   const ResidentArgs planes = resident ? split_planes(c, KS, Qb, Ib) : ResidentArgs{};
   for (size_t start = 0; start < nq; start += batch) {
     const size_t end = std::min(nq, start + batch), rows = end - start;

@@ -24,6 +24,17 @@ def _vp(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+def _check_failing(fn, *args, attr="failed_row"):
+    """check(fn(*args, &failed)) for the entry points that report where a factorisation failed: a ValueError leaves with
+    `attr` set to the smallest failing index, -1 unless the factorisation itself failed (an argument error)."""
+    failed = ctypes.c_int64(-1)
+    try:
+        check(fn(*args, ctypes.byref(failed)))
+    except ValueError as e:
+        setattr(e, attr, failed.value)
+        raise
+
+
 class RandomState:
     """_cuda.pyx:25-42"""
 
@@ -368,13 +379,7 @@ class LeastSquaresSolver:
     def least_squares_cholesky(self, cui, X, YtY, Y, regularization):
         """NEW: mirrors the CPU implicit.cpu._als._least_squares(YtY, ..., regularization): YtY is
         the UNregularised gramian; raises ValueError on a non-positive-definite row."""
-        failed = ctypes.c_int64(-1)
-        try:
-            check(lib().imp_solver_least_squares_cholesky(self._h, cui._h, X._h, YtY._h, Y._h,
-                                                          float(regularization), ctypes.byref(failed)))
-        except ValueError as e:
-            e.failed_row = failed.value  # -1 unless the factorisation itself failed (then: the smallest failing row)
-            raise
+        _check_failing(lib().imp_solver_least_squares_cholesky, self._h, cui._h, X._h, YtY._h, Y._h, float(regularization))
 
     def least_squares_subspace(self, cui, X, YtY, Y, regularization, block_size, sweeps=1):
         """NEW: the block-subspace half sweep of iALS++ for large factor counts: every row of X is improved, from its stored
@@ -382,25 +387,14 @@ class LeastSquaresSolver:
         times over.  YtY is the UNregularised gramian; float32 X and Y, at most 1024 factors.  block_size >= factors is the
         exact solve of least_squares_cholesky.  Raises ValueError (with .failed_row, -1 for an argument error) when a
         block's matrix is not positive definite; the other rows are solved."""
-        failed = ctypes.c_int64(-1)
-        try:
-            check(lib().imp_solver_least_squares_subspace(self._h, cui._h, X._h, YtY._h, Y._h, float(regularization),
-                                                          int(block_size), int(sweeps), ctypes.byref(failed)))
-        except ValueError as e:
-            e.failed_row = failed.value
-            raise
+        _check_failing(lib().imp_solver_least_squares_subspace, self._h, cui._h, X._h, YtY._h, Y._h, float(regularization),
+                       int(block_size), int(sweeps))
 
     def explain_factor(self, cui, YtY, Y, regularization, weights):
         """NEW: the Cholesky factor L of every row's A_u = YtY + regularization I + sum (|c| - 1) y y^T (YtY UNregularised, the
         matrix of least_squares_cholesky) into rows [u f, (u + 1) f) of `weights`, a float32 (cui.rows * f) x f Matrix: lower
         triangular, zeros above the diagonal.  f <= 256, Y float32.  ValueError (with .failed_row) on a non-positive pivot."""
-        failed = ctypes.c_int64(-1)
-        try:
-            check(lib().imp_solver_explain_factor(self._h, cui._h, YtY._h, Y._h, float(regularization), weights._h,
-                                                  ctypes.byref(failed)))
-        except ValueError as e:
-            e.failed_row = failed.value
-            raise
+        _check_failing(lib().imp_solver_explain_factor, self._h, cui._h, YtY._h, Y._h, float(regularization), weights._h)
 
     def explain(self, cui, Y, weights, itemids, items_per_row, n):
         """NEW: for row u of cui and each of its items_per_row ids in the IntVector `itemids` (row-major): the contributions
@@ -581,12 +575,7 @@ def spd_inverse(A):
     a workspace that cannot be allocated raises RuntimeError naming the bytes."""
     if not isinstance(A, Matrix):
         raise TypeError("spd_inverse: A must be an implicit_amd.gpu.Matrix")
-    failed = ctypes.c_int64(-1)
-    try:
-        check(lib().imp_spd_inverse(A._h, ctypes.byref(failed)))
-    except ValueError as e:
-        e.failed_pivot = failed.value  # -1 unless the factorisation itself failed
-        raise
+    _check_failing(lib().imp_spd_inverse, A._h, attr="failed_pivot")
     return A
 
 

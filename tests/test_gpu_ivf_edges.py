@@ -210,7 +210,7 @@ def test_second_trip(gpu):
     c.name = f"second_trip_{cus}"
     n, f = c.vectors.shape
     assert ic.tiles(1, c.claims["long"]) > ic.scan_grid(cus)  # one query's tiles of the long list alone
-    assert n * ic.f_pad(f) > ic.ivf_grid(n * ic.f_pad(f), 256, cus) * 256  # ivf_pad_kernel
+    assert n * ic.f_pad(f) > ic.ivf_grid(n * ic.f_pad(f), 256, cus) * 256  # ivf_pad (pad_rows_kernel)
     assert n * (ic.f_pad(f) // 4) > ic.ivf_grid(n * (ic.f_pad(f) // 4), 256, cus) * 256  # ivf_gather_rows_kernel
     _run(gpu, c)
 

@@ -134,6 +134,32 @@ def test_a_failing_block_names_the_smallest_row_and_spares_the_others(gpu, f, k,
     judge(f"sound problem after failing {failing} f={f} k={k}", again, y64[0], y32[0])
 
 
+@pytest.mark.parametrize("failing", cc.BLOCK_FAILING_SETS, ids=lambda s: "rows" + "_".join(map(str, s)))
+def test_a_failing_row_is_numbered_in_the_whole_matrix_across_row_blocks(gpu, monkeypatch, failing):
+    """The matrix held as four row blocks (rows 0 .. 14, 15, 16 .. 17, 18: the nonzeros per row are those of the Cholesky problem,
+    tests/test_cholesky_cases_host.py::test_block_limit_puts_the_failing_rows_in_three_blocks): a block reports a row numbered
+    inside the block, the call names the row of the whole matrix -- row 16 from the third block, row 15 from the second before
+    row 16 from the third, row 4 from the first."""
+    f, k = 64, 16
+    p = sc.failing_problem(f, tuple(failing))
+    x64, x32, bad = sc.reference("failing", f, k, 1, tuple(failing))
+    assert bad == sorted(failing)
+    C64 = p.C.copy()
+    C64.indptr = C64.indptr.astype(np.int64)
+    C64.indices = C64.indices.astype(np.int64)
+    monkeypatch.setenv("IMP_CSR_PART_NNZ", str(cc.BLOCK_NNZ))
+    blocks = gpu.CSRMatrix(C64)
+    monkeypatch.delenv("IMP_CSR_PART_NNZ")
+    Xd = gpu.Matrix(p.X0)
+    with pytest.raises(ValueError) as e:
+        gpu.LeastSquaresSolver().least_squares_subspace(blocks, Xd, gpu.Matrix(p.gram), gpu.Matrix(p.Y), p.reg, k, 1)
+    assert e.value.failed_row == min(failing), e.value
+    got, n = Xd.to_numpy(), p.C.shape[0]
+    sound = [u for u in range(n) if u not in failing]
+    judge(f"failing {failing} f={f} k={k} in row blocks, the other rows", got, x64[0], x32[0], rows=sound)
+    assert bits(got[n:]) == bits(p.X0[n:])
+
+
 # ---- 7. argument errors --------------------------------------------------------------------------------------------------------------
 def test_argument_errors_are_value_errors(gpu):
     p = sc.routes_problem(16)
