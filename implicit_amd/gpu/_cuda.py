@@ -10,7 +10,8 @@ NEW relative to the reference: LeastSquaresSolver.least_squares_cholesky (the re
 has no Cholesky solver), the Comm class (RCCL exchange for the multi-GPU fit), lmf_update (the
 reference has no GPU LMF), SpMat / sparse_topk_product (the reference's nearest-neighbour models are CPU only), IVFIndex
 (a native IVF-Flat index in place of the faiss one the reference's ann wrappers build) and ease_gram / spd_inverse /
-ease_weights / ease_topk (the EASE model, which the reference does not have).
+ease_weights / ease_topk (the EASE model, which the reference does not have), and spmm / multiply_small (the products of
+the randomized SVD behind PureSVD, which the reference does not have either).
 """
 import ctypes
 
@@ -612,6 +613,37 @@ def ease_topk(knn, B, rows, k, filter_liked=False, item_filter=None):
     check(lib().imp_ease_topk(knn._h, B._h, n, _vp(indptr), _vp(indices), _vp(data), k, 1 if filter_liked else 0,
                               item_filter._h if item_filter is not None else None, _vp(ids), _vp(scores)))
     return ids, scores
+
+
+def spmm(csr, dense, out=None):
+    """NEW: out = csr @ dense as a float32 device Matrix (imp_csr_spmm, svd.hip).  csr: a CSRMatrix (rows x cols); dense: a
+    float32 Matrix (cols x l), 1 <= l <= 1024.  Every entry is the fp32 sum of the row's products in stored order, rows of more
+    than 1024 entries in runs of 1024 that are added in order: defined bit for bit (tests/svd_reference.py restates it in
+    numpy).  `out`: a rows x l Matrix to write into (default: a new one); it must not overlap `dense`.  Shapes or dtypes that do
+    not agree raise ValueError with `out` untouched."""
+    if not isinstance(csr, CSRMatrix) or not isinstance(dense, Matrix):
+        raise TypeError("spmm expects an implicit_amd.gpu.CSRMatrix and an implicit_amd.gpu.Matrix")
+    if out is None:
+        out = Matrix.zeros(csr.shape[0], dense.shape[1])
+    elif not isinstance(out, Matrix):
+        raise TypeError("spmm: out must be an implicit_amd.gpu.Matrix")
+    check(lib().imp_csr_spmm(csr._h, dense._h, out._h))
+    return out
+
+
+def multiply_small(Y, W, out=None):
+    """NEW: out = Y @ W for a tall float32 Matrix Y (rows x l) and a small one W (l x m), 1 <= l, m <= 1024
+    (imp_matrix_multiply_small, svd.hip): exact fp32 products on the matrix cores in a fixed order, |out - exact| <=
+    (l + 1) 2^-24 sum |y w| per entry.  `out`: a rows x m Matrix to write into (default: a new one); it must not overlap Y
+    or W.  Shapes or dtypes that do not agree raise ValueError with `out` untouched."""
+    if not isinstance(Y, Matrix) or not isinstance(W, Matrix):
+        raise TypeError("multiply_small expects two implicit_amd.gpu.Matrix operands")
+    if out is None:
+        out = Matrix.zeros(Y.shape[0], W.shape[1])
+    elif not isinstance(out, Matrix):
+        raise TypeError("multiply_small: out must be an implicit_amd.gpu.Matrix")
+    check(lib().imp_matrix_multiply_small(Y._h, W._h, out._h))
+    return out
 
 
 def mem_get_info():

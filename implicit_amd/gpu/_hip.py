@@ -132,6 +132,8 @@ _SIGNATURES = {
     "imp_ease_weights": [ctypes.c_void_p],
     "imp_ease_topk": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    "imp_csr_spmm": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    "imp_matrix_multiply_small": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     "imp_comm_unique_id": [ctypes.c_void_p],
     "imp_comm_init_rank": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_void_pp],
     "imp_comm_destroy": [ctypes.c_void_p],

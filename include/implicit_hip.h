@@ -418,6 +418,24 @@ int imp_ease_topk(imp_knn *k, const imp_matrix *B, int32_t rows, const int64_t *
                   const float *data, int topk, int filter_liked, const imp_intvector *item_filter, int32_t *ids,
                   float *scores);
 
+/* ---- NEW: the two products of the randomized truncated SVD behind PureSVD (Cremonesi, Koren, Turrin 2010; Halko,
+ * Martinsson, Tropp 2011; no reference counterpart; csrc/svd.hip).  No floating-point atomics: equal inputs give
+ * bitwise equal outputs.  Both calls are synchronous and read no row schedule but A's. --------------------------------------- */
+/* out (caller-allocated fp32, rows x l) = A D for a CSR matrix A (rows x cols, fp32 values) and a dense fp32 D (cols x l),
+ * 1 <= l <= 1024.  For a row of at most 1024 stored entries (j_1, a_1), (j_2, a_2), ... out[r][c] is
+ * ((0 + a_1 D[j_1][c]) + a_2 D[j_2][c]) + ..., every product and every sum a separately rounded fp32 operation in stored
+ * order.  A longer row is cut into runs of 1024 stored entries; each run is summed that way from 0 and the runs' sums are then
+ * added in order, starting from the first run's.  An empty row gives zeros.  Exact when the values are integers and every
+ * partial sum stays below 2^24.  IMP_INVALID_ARGUMENT before any launch, out untouched: an operand that is not fp32, shapes
+ * that do not agree, l outside 1 .. 1024, more than 2^31 - 1 nonzeros, an out whose memory overlaps D's. */
+int imp_csr_spmm(const imp_csr *A, const imp_matrix *D, imp_matrix *out);
+/* out (caller-allocated fp32, rows x m) = Y W for a tall fp32 Y (rows x l) and a small fp32 W (l x m), 1 <= l, m <= 1024, on
+ * the fp32 matrix instruction: exact fp32 products, summed over the l terms in a fixed order.  |out - exact| <= (l + 1) 2^-24
+ * sum_i |y_i w_ij| per entry; exact when the values are integers and every partial sum stays below 2^24.  rows = 0 is a no-op.
+ * IMP_INVALID_ARGUMENT before any launch, out untouched: an operand that is not fp32, shapes that do not agree, l or m outside
+ * 1 .. 1024, an out whose memory overlaps Y's or W's. */
+int imp_matrix_multiply_small(const imp_matrix *Y, const imp_matrix *W, imp_matrix *out);
+
 /* ---- NEW: multi-GPU exchange over RCCL / xGMI (no reference counterpart) ------------------------ */
 /* One process per GPU.  Rank 0 calls imp_comm_unique_id, the host side broadcasts the 128 bytes by
  * any means (torch.distributed store, MPI, a file) and every rank calls imp_comm_init_rank. */
