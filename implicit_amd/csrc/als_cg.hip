@@ -622,9 +622,11 @@ static void cg_f64_f128(const imp_csr *C, T *X, const T *Y, size_t y_rows, const
   constexpr int f = 64 * VPL;
   // rows of more than 512 nonzeros through their explicit normal matrix on the matrix cores (als_cg_nm.hip).
   // IMP_NM=0: one streamed pass per CG step instead (A/B, parity; the workgroup clusters of rounds 2-3 are gone)
-  if (solver_switches().nm) least_squares_cg_nm<T>(C, X, Y, y_rows, A0, f, cg_steps);
+  // The finish of the rows cut into segments and the fix-up list come back as a pending tail: the class dispatch queues them.
+  NmTail tail;
+  if (solver_switches().nm) tail = least_squares_cg_nm<T>(C, X, Y, y_rows, A0, f, cg_steps);
   else launch_long<VPL, true, true, T>(C, C->plan_all, X, Y, A0, f, cg_steps);
-  least_squares_cg_q<T>(C, X, Y, A0, f, cg_steps);  // quarter-layout register tiles, wave teams (als_cg_q.hip)
+  least_squares_cg_q<T>(C, X, Y, A0, f, cg_steps, tail);  // quarter-layout register tiles, wave teams (als_cg_q.hip)
   zero_rows_t<T>(C->order.data(), C->first_empty(), C->n_empty(), X, f);
 }
 

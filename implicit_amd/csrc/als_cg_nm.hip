@@ -29,7 +29,9 @@
 //   * Rows of more than `segment` nonzeros (imp_csr::plan_nm: 2048 .. 16384, by the amount of long-row work) are cut into
 //     segments; their partial images go through a workspace, a second kernel sums them in segment order (one workgroup per
 //     sixteenth of an image) and a third runs the CG.  Every other row is finished by the workgroup that built its matrix.
-//     Segments are handed out by a ticket counter, longest first.
+//     Segments are handed out by a ticket counter, longest first.  (Where the half sweep goes on to the chained launches of
+//     fp32 storage at f = 128, those two kernels and the fix-up are not launched: the chains carry their work at their heads,
+//     launch_nm hands it over as an NmTail -- long_tail_route.h, als_nm_image.h.)
 //   * CG on the LDS image: the reference's recurrences (als.cu:45-109) with the product A_u p evaluated from the explicit matrix;
 //     256 threads, 256/f threads per matrix row.
 //
@@ -37,6 +39,7 @@
 // by the alternation of their two phases (conversion on the VALU, products on the matrix pipe: two workgroups per CU do not stay
 // in antiphase), not by memory: knock-outs and counters in DESIGN.md section 4.2.  IMP_NM=0 restores the cluster + streamed
 // kernels (A/B, parity).
+#include "als_nm_image.h"  // NmShape, NmLayout, nm_cg
 #include "als_qf_common.h"
 #include "common.h"
 #include "wave_ops.h"
@@ -45,46 +48,6 @@ namespace imp {
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int F> struct NmShape;
-template <> struct NmShape<128> {
-  static constexpr int M = 32, KG = 2, NACC = 16;
-  using acc_t = f32x16;
-  __device__ static __forceinline__ acc_t mfma(half8 a, half8 b, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-  // C/D layout of the 32 x 32 tile: column = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
-  __device__ static __forceinline__ int row(int lane, int e) { return (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }
-  __device__ static __forceinline__ int col(int lane) { return lane & 31; }
-};
-template <> struct NmShape<64> {
-  static constexpr int M = 16, KG = 4, NACC = 4;
-  using acc_t = f32x4v;
-  __device__ static __forceinline__ acc_t mfma(half8 a, half8 b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-  // 16 x 16 tile: column = lane & 15, row = 4 (lane >> 4) + e
-  __device__ static __forceinline__ int row(int lane, int e) { return 4 * (lane >> 4) + e; }
-  __device__ static __forceinline__ int col(int lane) { return lane & 15; }
-};
-
-template <int F> struct NmLayout {
-  static constexpr int M = F / 4;              // rows of a tile
-  static constexpr int TS = M + 1;             // row stride inside a tile: rows m and columns n both walk all LDS banks
-  static constexpr int IMG = 16 * M * TS;      // floats of the image: 16 tiles (I, J), tile (I, J)[m][n] = A[4m+I][4n+J]
-  static constexpr int KCH = 8 * NmShape<F>::KG;  // nonzeros per step (one wavefront's gathers)
-  static constexpr int ROUND = 4 * KCH;        // nonzeros per round: one step from each of the four wavefronts
-  static constexpr int kTiles = 10;            // (I, J), I >= J
-  static constexpr int kSlots = 3;             // tiles per wavefront: 3, 3, 2, 2
-  // operand exchange: [step][kind: uh ul yh yl][block][lane] quads of 16 bytes
-  static constexpr int QUAD = 64 * 4;          // floats of one operand quad (one b128 per lane)
-  static constexpr int OPS = 4 * 16 * QUAD;    // floats of the exchange buffer (64 KB); the image re-uses the space afterwards
-  static constexpr int NP = 256 / F;           // thread groups sharing a matrix row in the CG phase
-  static constexpr int kVec = IMG > OPS ? IMG : OPS;  // offset of the vectors behind the image / exchange buffer
-  static constexpr size_t lds_floats = (size_t)kVec + 2 * F + NP * F + 64 + 4 * F;  // image / operands | b | p | partial products | reduction slots | b per wavefront
-  __host__ __device__ static constexpr int at(int I, int J, int m, int n) { return ((I * 4 + J) * M + m) * TS + n; }
-};
 __device__ constexpr int nm_tile_i(int t) { return t < 1 ? 0 : t < 3 ? 1 : t < 6 ? 2 : 3; }
 __device__ constexpr int nm_tile_j(int t) { return t - (nm_tile_i(t) * (nm_tile_i(t) + 1)) / 2; }
 
@@ -425,75 +388,6 @@ __device__ __forceinline__ void nm_build(const int32_t *__restrict__ indices, co
     }
   }
   __syncthreads();
-}
-
-// ---- CG on the LDS image (als.cu:45-109 with A_u p from the explicit matrix) ----------------------------------------------------
-// Vectors live in image order: position r = I M + m is factor 4m + I.  Thread (r = tid % F, grp = tid / F) forms the products of
-// row r with the column blocks J of its group: lanes walk m, i.e. consecutive tile rows of stride M + 1 -- conflict-free.
-template <int F, typename T>
-__device__ __forceinline__ bool nm_cg(const float *img, const float *bvec, float *pv, float *parts, float *red, T *xrow, int cg_steps, int tid) {
-  using L = NmLayout<F>;
-  constexpr int M = L::M, NP = L::NP, JPG = 4 / NP;
-  const int r = tid % F, grp = tid / F, lane = tid & 63, wave = tid >> 6;
-  const int I = r / M, m = r % M;
-  int slot = 0;
-  auto matvec = [&]() {
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int jj = 0; jj < JPG; ++jj) {
-      const int J = grp * JPG + jj;
-      const float *row = img + L::at(I, J, m, 0);
-#pragma unroll
-      for (int n = 0; n < M; n += 4) {
-        const float4 p4 = *reinterpret_cast<const float4 *>(pv + J * M + n);
-        s[0] = fmaf(row[n], p4.x, s[0]), s[1] = fmaf(row[n + 1], p4.y, s[1]);
-        s[2] = fmaf(row[n + 2], p4.z, s[2]), s[3] = fmaf(row[n + 3], p4.w, s[3]);
-      }
-    }
-    parts[grp * F + r] = (s[0] + s[1]) + (s[2] + s[3]);
-    __syncthreads();
-    float q = parts[r];
-#pragma unroll
-    for (int gq = 1; gq < NP; ++gq) q += parts[gq * F + r];
-    return q;
-  };
-  auto block_sum = [&](float v) {  // over the F positions (the threads of group 0 contribute)
-    v = wave_allsum(grp == 0 ? v : 0.f);
-    if (lane == 0) red[4 * slot + wave] = v;
-    __syncthreads();
-    const float s = (red[4 * slot] + red[4 * slot + 1]) + (red[4 * slot + 2] + red[4 * slot + 3]);
-    slot = (slot + 1) & 7;
-    return s;
-  };
-  // Operands beyond the fp16 range leave infinities in the image; whatever they touch stops being finite.  The squared norms
-  // below see every component of every residual and of every A p (through p.Ap) -- one non-finite value in them and the row is
-  // NOT stored: the caller lists it for the fp32 fix-up kernel.  (A row whose inputs are not finite to begin with takes the same
-  // way and gets the reference's own non-finite answer there.)
-  auto finite = [](float v) { return fabsf(v) <= 3.0e38f; };
-  float x = load1(xrow + 4 * m + I);
-  if (grp == 0) pv[r] = x;
-  __syncthreads();
-  float res = bvec[r] - matvec();
-  float p = res;
-  float rsold = block_sum(res * res);
-  if (!finite(rsold)) return true;
-  if (rsold < 1e-20f) return false;
-  for (int it = 0; it < cg_steps; ++it) {
-    if (grp == 0) pv[r] = p;
-    __syncthreads();
-    const float Ap = matvec();
-    const float pAp = block_sum(p * Ap);
-    const float alpha = rsold / pAp;
-    x = fmaf(alpha, p, x);
-    res = fmaf(-alpha, Ap, res);
-    const float rsnew = block_sum(res * res);
-    if (!finite(pAp) || !finite(rsnew) || !finite(alpha)) return true;
-    if (rsnew < 1e-20f) break;
-    p = fmaf(rsnew / rsold, p, res);
-    rsold = rsnew;
-  }
-  if (grp == 0) store1(xrow + 4 * m + I, x);
-  return false;
 }
 
 #ifdef CHOL_NM_STATS  // timing-only build: shader-clock cycles per phase of als_chol_nm_rows_kernel, wave 0 lane 0 of every workgroup
@@ -850,11 +744,13 @@ __global__ __launch_bounds__(256, 2) void als_chol_nm_rows_kernel(const int32_t 
   }
 }
 
-template <int F, typename T> void launch_nm(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int cg_steps) {
+// Queues the gramian image and the normal-matrix kernel and hands back what is pending behind them (NmTail, common.h): the
+// finish of the rows of more than one segment and the fix-up of the listed rows.  The class dispatch queues both -- as the
+// heads of its chained launches, or as the stand-alone kernels below (long_tail_route.h).
+template <int F, typename T> NmTail launch_nm(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int cg_steps) {
   const LongPlan &lp = C->plan_nm;
-  if (lp.n_seg <= 0) return;
+  if (lp.n_seg <= 0) return NmTail{};
   using L = NmLayout<F>;
-  static_assert(L::IMG % 4 == 0, "the image is copied in 16-byte pieces");
   const size_t lds = L::lds_floats * sizeof(float);
   const int n_multi = C->nm_multi_rows, n_multi_seg = C->nm_multi_segs;
   const size_t need = (size_t)L::IMG + (size_t)n_multi_seg * (L::IMG + F);  // gramian image | partial images
@@ -865,9 +761,7 @@ template <int F, typename T> void launch_nm(const imp_csr *C, T *X, const T *Y, 
   fix.reserve((size_t)lp.n_long);
   LongPlanDev plan = lp.dev(C->order.data());
   auto kern = als_cg_nm_kernel<F, T>;
-  auto fin = als_cg_nm_finish_kernel<F, T>;
   allow_dynamic_lds(kern, lds);
-  allow_dynamic_lds(fin, lds);
   {
     IMP_PROF("als_cg_nm_rows");
     constexpr int forced_k = -1;  // (>= 0: a fixed operand scale 2^k instead of the one taken from the gramian's diagonal)
@@ -877,14 +771,26 @@ template <int F, typename T> void launch_nm(const imp_csr *C, T *X, const T *Y, 
     kern<<<grid, 256, lds, stream()>>>(plan, C->indices.data(), C->data.data(), X, Y, gram_img, cg_steps, partial, tk.data(), fix.data(), ko);
     IMP_CHECK_HIP(hipGetLastError());
   }
-  if (n_multi > 0) {
-    IMP_PROF("als_cg_nm_finish");
-    als_cg_nm_reduce_kernel<F><<<std::min(n_multi * 16, ctx().num_cus * 16), 256, 0, stream()>>>(plan, n_multi, gram_img, partial);
-    fin<<<std::min(n_multi, ctx().num_cus * 2), 256, lds, stream()>>>(plan, n_multi, X, cg_steps, partial, tk.data(), fix.data());
-    IMP_CHECK_HIP(hipGetLastError());
-  }
-  // rows whose operands left the fp16 range (normally none: the kernel reads a zero and exits)
-  launch_cg_fixup<F, T>(reinterpret_cast<const unsigned *>(tk.data() + 2), fix.data(), lp.n_long, C, X, Y, A0, cg_steps);
+  NmTail tail;
+  tail.plan = plan, tail.n_multi = n_multi, tail.gram_img = gram_img, tail.partial = partial;
+  tail.ctl = tk.data(), tail.fix_rows = fix.data(), tail.capacity = lp.n_long;
+  return tail;
+}
+
+// the rows of more than one segment in two launches of their own: the sum of a row's partial images, then the CG on it
+template <int F, typename T> void launch_nm_finish(const NmTail &tail, T *X, int cg_steps) {
+  if (tail.n_multi <= 0) return;
+  using L = NmLayout<F>;
+  static_assert(L::IMG % 4 == 0, "the image is copied in 16-byte pieces");
+  const size_t lds = L::lds_floats * sizeof(float);
+  auto fin = als_cg_nm_finish_kernel<F, T>;
+  allow_dynamic_lds(fin, lds);
+  IMP_PROF("als_cg_nm_finish");
+  als_cg_nm_reduce_kernel<F><<<std::min(tail.n_multi * 16, ctx().num_cus * 16), 256, 0, stream()>>>(tail.plan, tail.n_multi, tail.gram_img,
+                                                                                                  tail.partial);
+  fin<<<std::min(tail.n_multi, ctx().num_cus * 2), 256, lds, stream()>>>(tail.plan, tail.n_multi, X, cg_steps, tail.partial, tail.ctl,
+                                                                         tail.fix_rows);
+  IMP_CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace
@@ -949,12 +855,20 @@ CholNmList least_squares_cholesky_nm(const imp_csr *C, float *X, const float *Y,
   return CholNmList{reinterpret_cast<const unsigned *>(tk.data() + 2), fix.data(), capacity};
 }
 
-template <typename T> void least_squares_cg_nm(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int f, int cg_steps) {
-  if (f == 128) launch_nm<128, T>(C, X, Y, y_rows, A0, cg_steps);
-  else if (f == 64) launch_nm<64, T>(C, X, Y, y_rows, A0, cg_steps);
-  else throw std::invalid_argument("least_squares_cg_nm: f must be 64 or 128");
+template <typename T> NmTail least_squares_cg_nm(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int f, int cg_steps) {
+  if (f == 128) return launch_nm<128, T>(C, X, Y, y_rows, A0, cg_steps);
+  if (f == 64) return launch_nm<64, T>(C, X, Y, y_rows, A0, cg_steps);
+  throw std::invalid_argument("least_squares_cg_nm: f must be 64 or 128");
 }
-template void least_squares_cg_nm<float>(const imp_csr *, float *, const float *, size_t, const float *, int, int);
-template void least_squares_cg_nm<__half>(const imp_csr *, __half *, const __half *, size_t, const float *, int, int);
+template NmTail least_squares_cg_nm<float>(const imp_csr *, float *, const float *, size_t, const float *, int, int);
+template NmTail least_squares_cg_nm<__half>(const imp_csr *, __half *, const __half *, size_t, const float *, int, int);
+
+template <typename T> void cg_nm_finish(const NmTail &tail, T *X, int f, int cg_steps) {
+  if (f == 128) launch_nm_finish<128, T>(tail, X, cg_steps);
+  else if (f == 64) launch_nm_finish<64, T>(tail, X, cg_steps);
+  else throw std::invalid_argument("cg_nm_finish: f must be 64 or 128");
+}
+template void cg_nm_finish<float>(const NmTail &, float *, int, int);
+template void cg_nm_finish<__half>(const NmTail &, __half *, int, int);
 
 }  // namespace imp

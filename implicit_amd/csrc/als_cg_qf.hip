@@ -8,6 +8,8 @@
 
 #include <algorithm>
 
+#include "als_cg_fixup.h"
+#include "als_nm_image.h"
 #include "als_qf_common.h"
 #include "common.h"
 
@@ -81,6 +83,11 @@ static void launch_qfteam(const imp_csr *C, int first, int count, T *X, const T 
 // longest-first, so tickets balance a class dynamically, and a workgroup that runs out of one class starts the next at
 // once.  No workgroup waits for another; the counters of the classes' queues are the only global state, and they are never
 // reset (team_tickets.h).  Every row's arithmetic is that of its class kernel, and no row depends on which team solves it, or when.
+//
+// At its head the launch carries the FINISH ITEMS of the long-row path (nm_finish_items, als_nm_image.h; long_tail_route.h says
+// when): the normal-matrix kernel has ended behind a kernel boundary, workgroup b sums the partial images of the rows b,
+// b + grid, ... into the LDS this launch holds anyway and runs their CG there, wavefronts 4 - 7 idle at the barriers.  A few
+// hundred items of 10 - 100 us ahead of ticketed classes of a millisecond: the tickets absorb them.
 struct ChainClassArgs {
   int first[ChainTickets::kClasses], count[ChainTickets::kClasses];
   unsigned base[ChainTickets::kClasses][ChainTickets::kQueues];
@@ -96,8 +103,13 @@ __global__ __launch_bounds__(512, F == 64 ? 8 : 4) void als_cg_qfteam_chain_kern
                                                                                   const int32_t *__restrict__ indices,
                                                                                   const float *__restrict__ data, ST *__restrict__ X,
                                                                                   const ST *__restrict__ Y, const float *__restrict__ A0,
-                                                                                  int cg_steps) {
+                                                                                  int cg_steps, NmFinishArgs finish) {
   static_assert(Tile32<ST>::T == 32, "chain_lds_bytes");
+  static_assert(NmLayout<F>::lds_floats * sizeof(float) <= chain_lds_bytes<F>(), "the finish items work in the chain's own LDS");
+  if (finish.n_multi > 0) {  // uniform over the grid
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    nm_finish_items<F, ST, 512>(finish, X, cg_steps, smem);  // returns behind a barrier: the gramian may overwrite the image
+  }
   team_stage_gramian<F, 512>(A0);
   bool entered = false;  // a class has run: its LDS layout is live until every wavefront of the workgroup has left it
   static_for<ChainTickets::kClasses>([&](auto Cc) {
@@ -117,11 +129,17 @@ static int team512_per_cu(size_t lds) { return (int)std::max<size_t>(1, std::min
 
 template <typename T>
 void launch_team_chain(const imp_csr *C, int f, const int (&first)[3], const int (&count)[3], T *X, const T *Y, const float *A0, int cg_steps,
-                       const char *name) {
+                       const char *name, const NmTail *finish) {
   if constexpr (std::is_same<T, float>::value) {
     auto run = [&](auto Fc) {
       constexpr int F = decltype(Fc)::value;
-      if (count[0] <= 0 && count[1] <= 0 && count[2] <= 0) return;
+      if (count[0] <= 0 && count[1] <= 0 && count[2] <= 0) {
+        if (finish) throw std::logic_error("launch_team_chain: finish items without a launch to carry them");
+        return;
+      }
+      NmFinishArgs fin;
+      if (finish)
+        fin = NmFinishArgs{finish->n_multi, finish->plan.rows, finish->plan.row_seg, finish->gram_img, finish->partial, finish->ctl, finish->fix_rows};
       const size_t lds = chain_lds_bytes<F>();
       auto kern = als_cg_qfteam_chain_kernel<F, T>;
       allow_dynamic_lds(kern, lds);
@@ -140,12 +158,12 @@ void launch_team_chain(const imp_csr *C, int f, const int (&first)[3], const int
       after.launch(cls.count, grid, teams, cls.base);
       IMP_PROF(name);
       kern<<<grid, 512, lds, stream()>>>(C->order.data(), cls, cx.chain_counters.data(), C->indptr.data(), C->indices.data(),
-                                        C->data.data(), X, Y, A0, cg_steps);
+                                        C->data.data(), X, Y, A0, cg_steps, fin);
       IMP_CHECK_HIP(hipGetLastError());
       cx.chain_tickets = after;  // a launch that was not queued draws nothing
     };
     // f = 64 keeps its per-class launches: its team kernels sit exactly at the 64 registers of 8 waves per SIMD, and the three
-    // row loops in one kernel do not fit (the chain compiles to 32 bytes of scratch per lane there; none at f = 128: 126 VGPRs)
+    // row loops in one kernel do not fit (the chain compiles to 32 bytes of scratch per lane there; none at f = 128: 127 VGPRs)
     if (f == 128) run(idx_t<128>{});
     else throw std::invalid_argument("launch_team_chain: f must be 128");
   } else {
@@ -153,9 +171,9 @@ void launch_team_chain(const imp_csr *C, int f, const int (&first)[3], const int
   }
 }
 template void launch_team_chain<float>(const imp_csr *, int, const int (&)[3], const int (&)[3], float *, const float *, const float *, int,
-                                       const char *);
+                                       const char *, const NmTail *);
 template void launch_team_chain<__half>(const imp_csr *, int, const int (&)[3], const int (&)[3], __half *, const __half *, const float *,
-                                        int, const char *);
+                                        int, const char *, const NmTail *);
 
 // ---- short rows (<= 32 nnz) at f = 128: one wave per row, 16 rows per workgroup in lock step --------------------------------
 // The waves publish their operands in LDS; the dense part of a pass is ONE product A0 . P^T for the 16 rows, its 16-factor output
@@ -552,6 +570,11 @@ static void launch_qfgroup(const imp_csr *C, int first, int count, T *X, const T
 // gramian as bf16 planes over the same allocation and runs groups of short rows by ticket (group_rows, TICKETS).  The ticket
 // bookkeeping is WideTickets (team_tickets.h).  Every row's arithmetic is that of its class kernel.
 //
+// At its head the launch carries the FIX-UP of the long-row path (long_tail_route.h says when): every launch that can list a row
+// has ended behind a kernel boundary, so the count every workgroup reads is complete.  It is normally zero -- one scalar load.
+// Otherwise the 16 wavefronts of workgroup b take the listed rows i = 16 b + wave, + 16 grid, ... through cg_fixup_row
+// (als_cg_fixup.h) on F floats of LDS each, and one barrier hands the allocation to the classes.
+//
 // IMP_WIDE_FORM (compile time, A/B builds): 0 the chain with tickets in both classes; 1 the chain with the short rows' groups
 // dealt in fixed strides over the resident grid; 2 no chain: each class in a launch of its own on the resident grid, with tickets.
 #ifndef IMP_WIDE_FORM
@@ -560,6 +583,11 @@ static void launch_qfgroup(const imp_csr *C, int first, int count, T *X, const T
 struct WideClassArgs {
   int first[WideTickets::kClasses], count[WideTickets::kClasses];  // rows
   unsigned base[WideTickets::kClasses][WideTickets::kQueues];
+};
+struct WideFixupArgs {  // the fix list of the long-row path, re-solved at the head of the launch
+  const unsigned *count = nullptr, *rows = nullptr;
+  int capacity = 0;  // 0: no fix-up in this launch
+  unsigned long long *total = nullptr;  // host-mapped: rows re-solved (fixup_total)
 };
 static_assert(WideTickets::kQueues == kTicketQueues && WideTickets::kGroupRows == 16, "queues and groups of the ticketed classes");
 // the larger of the two layouts; the short rows' ticket word follows theirs
@@ -573,7 +601,19 @@ __global__ __launch_bounds__(1024) void als_cg_qfwide_chain_kernel(const int32_t
                                                                    const int32_t *__restrict__ indices,
                                                                    const float *__restrict__ data, ST *__restrict__ X,
                                                                    const ST *__restrict__ Y, const float *__restrict__ A0,
-                                                                   int cg_steps) {
+                                                                   int cg_steps, WideFixupArgs fix) {
+  if (fix.capacity > 0) {  // uniform over the grid, as is n
+    const int n = min((int)fix.count[0], fix.capacity);
+    if (n != 0) {
+      extern __shared__ __attribute__((aligned(16))) float smem[];
+      if (blockIdx.x == 0 && threadIdx.x == 0)
+        __hip_atomic_fetch_add(fix.total, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+      for (int i = blockIdx.x * 16 + wave; i < n; i += gridDim.x * 16)
+        cg_fixup_row<F, ST>(smem + wave * F, lane, (int)fix.rows[i], indptr, indices, data, X, Y, A0, cg_steps);
+      __syncthreads();  // every wavefront has left its operand slot
+    }
+  }
   const unsigned queue = blockIdx.x % kTicketQueues;
   if (cls.count[0] > 0)  // uniform over the grid
     team_rows<Tile32<ST>, F, 16, 1024, true, true>(order, cls.first[0], cls.count[0], indptr, indices, data, X, Y, A0, cg_steps,
@@ -588,12 +628,19 @@ __global__ __launch_bounds__(1024) void als_cg_qfwide_chain_kernel(const int32_t
 
 template <typename T>
 void launch_wide_chain(const imp_csr *C, int f, const int (&first)[2], const int (&count)[2], T *X, const T *Y, const float *A0, int cg_steps,
-                       const char *name) {
+                       const char *name, const NmTail *fixup) {
   if constexpr (std::is_same<T, float>::value) {
     if (f != 128) throw std::invalid_argument("launch_wide_chain: f must be 128");
     constexpr int F = 128;
     constexpr bool kShortTickets = IMP_WIDE_FORM != 1;
-    if (count[0] <= 0 && count[1] <= 0) return;
+    if (count[0] <= 0 && count[1] <= 0) {
+      if (fixup) throw std::logic_error("launch_wide_chain: a fix-up without a launch to carry it");
+      return;
+    }
+    static_assert(16 * F * sizeof(float) <= wide_chain_lds_bytes<F>(), "an operand slot per wavefront of the fix-up");
+    WideFixupArgs fix;  // carried by the first launch queued here
+    if (fixup && fixup->capacity > 0)
+      fix = WideFixupArgs{reinterpret_cast<const unsigned *>(fixup->ctl + 2), fixup->fix_rows, fixup->capacity, fixup_total()};
     const size_t lds = wide_chain_lds_bytes<F>();
     auto kern = als_cg_qfwide_chain_kernel<F, T, kShortTickets>;
     // the resident workgroups per CU, asked of the runtime once per process (registers and LDS allow one)
@@ -622,8 +669,9 @@ void launch_wide_chain(const imp_csr *C, int f, const int (&first)[2], const int
       const int32_t ticketed[2] = {rows[0], kShortTickets ? rows[1] : 0};
       after.launch_rows(ticketed, grid, cls.base);
       kern<<<grid, 1024, lds, stream()>>>(C->order.data(), cls, cx.wide_counters.data(), C->indptr.data(), C->indices.data(),
-                                         C->data.data(), X, Y, A0, cg_steps);
+                                         C->data.data(), X, Y, A0, cg_steps, fix);
       IMP_CHECK_HIP(hipGetLastError());
+      fix = WideFixupArgs{};
       cx.wide_tickets = after;  // a launch that was not queued draws nothing
     };
     IMP_PROF(name);
@@ -634,9 +682,9 @@ void launch_wide_chain(const imp_csr *C, int f, const int (&first)[2], const int
   }
 }
 template void launch_wide_chain<float>(const imp_csr *, int, const int (&)[2], const int (&)[2], float *, const float *, const float *, int,
-                                       const char *);
+                                       const char *, const NmTail *);
 template void launch_wide_chain<__half>(const imp_csr *, int, const int (&)[2], const int (&)[2], __half *, const __half *, const float *,
-                                        int, const char *);
+                                        int, const char *, const NmTail *);
 
 template <typename T>
 void launch_group_fused(const imp_csr *C, int f, int first, int count, T *X, const T *Y, const float *A0, int cg_steps, const char *name) {

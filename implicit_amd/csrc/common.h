@@ -404,10 +404,24 @@ void gramian_half(const void *Y, long n_rows, int f, float reg, float *out);  //
 // als_cg.hip and the kernels it dispatches to
 bool cg_native_half(int f);
 void least_squares_cg(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, int cg_steps);
-template <typename T> void least_squares_cg_q(const imp_csr *C, T *X, const T *Y, const float *A0, int f, int cg_steps);  // als_cg_q.hip
+// What is pending behind the normal-matrix kernel of a CG half sweep (als_cg_nm.hip), handed from its launcher to the class
+// dispatch, which decides who runs it (long_tail_route.h): the first n_multi rows of the plan were built in more than one
+// segment and wait for the sum of their partial images and the CG on it; rows a solve could not finish in fp16-split operands
+// are listed in fix_rows (ctl[2] counts them, at most `capacity`) for the fp32 fix-up.
+struct NmTail {
+  LongPlanDev plan{};
+  int n_multi = 0;
+  float *gram_img = nullptr, *partial = nullptr;
+  int *ctl = nullptr;
+  unsigned *fix_rows = nullptr;
+  int capacity = 0;  // 0: no normal-matrix launch, nothing is pending
+};
+// als_cg_q.hip: the classes below the long rows, and the tail of the long rows
+template <typename T> void least_squares_cg_q(const imp_csr *C, T *X, const T *Y, const float *A0, int f, int cg_steps, const NmTail &tail);
 void least_squares_cg_w256(const imp_csr *C, float *X, const float *Y, const float *A0, int cg_steps);                    // als_cg_w256.hip
-template <typename T>
-void least_squares_cg_nm(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int f, int cg_steps);  // als_cg_nm.hip
+// als_cg_nm.hip: the gramian image and the normal-matrix kernel, queued; cg_nm_finish: the stand-alone reduce + finish of its tail
+template <typename T> NmTail least_squares_cg_nm(const imp_csr *C, T *X, const T *Y, size_t y_rows, const float *A0, int f, int cg_steps);
+template <typename T> void cg_nm_finish(const NmTail &tail, T *X, int f, int cg_steps);
 // als_cholesky.hip, als_subspace.hip: -1, or the smallest failing row of the block
 int64_t least_squares_cholesky(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg);
 int64_t least_squares_subspace(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg, int block_size,

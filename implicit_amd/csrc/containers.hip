@@ -13,6 +13,7 @@
 #include <thread>
 
 #include "common.h"
+#include "long_tail_route.h"
 
 namespace imp {
 
@@ -673,6 +674,23 @@ int imp_host_wide_tickets(uint32_t *next, const int32_t *rows, int32_t workgroup
         draws[k * NQ + q] = t.next[k][q] - next[k * NQ + q];
         next[k * NQ + q] = t.next[k][q], base[k * NQ + q] = b[k][q];
       }
+  });
+}
+
+// ---- host-side helper: who runs the tail of the long-row path of a CG half sweep (long_tail_route.h) --
+// out[2] = {finish, fixup} in the numbering of LongTailRoute.
+int imp_host_long_tail_route(const int32_t *chain_count, const int32_t *wide_count, int32_t n_multi, int32_t capacity, int32_t chained,
+                             int32_t *out) {
+  return guarded_host([&] {
+    if (n_multi < 0 || capacity < 0 || n_multi > capacity)
+      throw std::invalid_argument("host_long_tail_route: 0 <= n_multi <= capacity (the rows of more than one segment are long rows)");
+    for (int k = 0; k < 3; ++k)
+      if (chain_count[k] < 0) throw std::invalid_argument("host_long_tail_route: a class holds no fewer than 0 rows");
+    for (int k = 0; k < 2; ++k)
+      if (wide_count[k] < 0) throw std::invalid_argument("host_long_tail_route: a class holds no fewer than 0 rows");
+    const int32_t chain[3] = {chain_count[0], chain_count[1], chain_count[2]}, wide[2] = {wide_count[0], wide_count[1]};
+    const LongTailRoute r = long_tail_route(chain, wide, n_multi, capacity, chained != 0);
+    out[0] = r.finish, out[1] = r.fixup;
   });
 }
 

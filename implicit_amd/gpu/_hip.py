@@ -40,6 +40,7 @@ _SIGNATURES = {
                           ctypes.c_void_p],
     "imp_host_chain_tickets": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     "imp_host_wide_tickets": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p],
+    "imp_host_long_tail_route": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p],
     "imp_matrix_create": [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_void_pp],
     "imp_matrix_wrap_device": [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, c_void_pp],
     "imp_matrix_row": [ctypes.c_void_p, ctypes.c_size_t, c_void_pp],

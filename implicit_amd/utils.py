@@ -210,3 +210,19 @@ def wide_tickets(state, rows, workgroups):
     base, draws = np.empty((2, 8), np.uint32), np.empty((2, 8), np.uint32)
     check(lib().imp_host_wide_tickets(state.ctypes.data, rows.ctypes.data, int(workgroups), base.ctypes.data, draws.ctypes.data))
     return base, draws
+
+
+def long_tail_route(chain_counts, wide_counts, n_multi, capacity, chained):
+    """Who runs the tail of the long-row path of a CG half sweep (imp_host_long_tail_route, host code) for the row counts of the
+    three chained 512-thread classes and the two 1024-thread ones, `n_multi` long rows of more than one segment, a fix list of
+    `capacity` entries, on the chained route or not.  Returns (finish, fixup): finish 0 nothing, 1 stand-alone, 2 the team
+    chain; fixup 0 nothing, 1 stand-alone ahead of the classes, 2 stand-alone behind the team chain, 3 the wide chain."""
+    from .gpu._hip import check, lib
+
+    chain = np.ascontiguousarray(chain_counts, dtype=np.int32)
+    wide = np.ascontiguousarray(wide_counts, dtype=np.int32)
+    assert chain.shape == (3,) and wide.shape == (2,)
+    out = np.zeros(2, np.int32)
+    check(lib().imp_host_long_tail_route(chain.ctypes.data, wide.ctypes.data, int(n_multi), int(capacity), int(bool(chained)),
+                                         out.ctypes.data))
+    return int(out[0]), int(out[1])

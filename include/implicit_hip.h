@@ -120,6 +120,14 @@ int imp_host_chain_tickets(uint32_t *next, const int32_t *count, int32_t workgro
  * (0 .. 2^30 - 1 each), workgroups (> 0); outputs base[2][8] and draws[2][8]. */
 int imp_host_wide_tickets(uint32_t *next, const int32_t *rows, int32_t workgroups, uint32_t *base, uint32_t *draws);
 
+/* Host code, no device involved: who runs the tail of the long-row path of a CG half sweep (csrc/long_tail_route.h).
+ * chain_count[3]: rows of (128,256], (64,128], (32,64]; wide_count[2]: rows of (256,512] and short rows; n_multi: long rows of
+ * more than one segment; capacity: entries of the fix list (0 <= n_multi <= capacity); chained: non-zero where the half sweep
+ * takes the two chained launches.  out[0]: 0 nothing to finish, 1 stand-alone reduce + finish, 2 the head of the team chain;
+ * out[1]: 0 no fix-up, 1 stand-alone ahead of the classes, 2 stand-alone behind the team chain, 3 the head of the wide chain. */
+int imp_host_long_tail_route(const int32_t *chain_count, const int32_t *wide_count, int32_t n_multi, int32_t capacity, int32_t chained,
+                             int32_t *out);
+
 /* ---- Matrix (matrix.h:23-90, matrix.cu:34-220) -------------------------------------------- */
 /* Matrix(rows, cols, data, allocate=true, itemsize): allocates; copies rows*cols*itemsize bytes
  * from host_data when non-NULL, zero-fills otherwise (matrix.cu:80-96). */
