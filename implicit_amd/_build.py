@@ -15,7 +15,7 @@ OBJDIR = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libimplicit_hip.so")
 SOURCES = ["containers.hip", "csr_schedule.hip", "als_cg.hip", "als_cg_q.hip", "als_cg_qf.hip", "als_cg_qh.hip", "als_cg_fixup.hip", "als_cg_nm.hip", "als_cg_w256.hip", "als_pad.hip", "als_cholesky.hip", "als_subspace.hip", "gramian.hip", "solver.hip", "topk.hip",
            "random.hip", "comm.hip", "pair_sgd.hip", "bpr.hip", "warp.hip", "lmf.hip", "knn.hip", "evaluation.hip", "ivf.hip", "explain.hip", "rank.hip",
-           "ease.hip", "spd_inverse.hip", "svd.hip"]
+           "ease.hip", "spd_inverse.hip", "svd.hip", "slim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-pass-failed", "-ffp-contract=off"]

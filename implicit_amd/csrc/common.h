@@ -228,6 +228,9 @@ struct Context {
   int knn_cols = -1;                             // column count knn_acc is laid out for
   DeviceArray<float> subspace_pred;              // predictions of a subspace half sweep, one per nonzero in CSR order (als_subspace.hip)
   DeviceArray<float> subspace_ws;                // its long rows' segment partials, block steps and failure flags
+  DeviceArray<float> slim_diag;                  // the diagonal of A, copied aside by the check of imp_slim_solve (slim.hip)
+  DeviceArray<int32_t> slim_ws;                  // its column order, sweep counts, ticket and the two counts of imp_slim_stats
+  size_t slim_items = 0;                         // order of the last imp_slim_solve: where the counts sit in slim_ws
 };
 inline hipStream_t stream() { return ctx().stream; }
 

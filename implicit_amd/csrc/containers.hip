@@ -490,6 +490,9 @@ int imp_release_workspaces(void) {
     c.w256_ws = {};
     c.subspace_pred = {};
     c.subspace_ws = {};
+    c.slim_diag = {};
+    c.slim_ws = {};
+    c.slim_items = 0;
     std::lock_guard<std::mutex> g(c.small_mutex);
     for (auto &list : c.small_free) {
       for (void *p : list) (void)hipFree(p);

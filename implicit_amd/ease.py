@@ -32,6 +32,8 @@ class EASE(RecommenderBase):
     After fit(): item_weights, a float32 items x items implicit_amd.gpu.Matrix B with a zero diagonal; column j holds the
     ridge regression of item j on every other item."""
 
+    _name = "EASE"  # what the error texts call the model (SLIM shares the serving half)
+
     def __init__(self, regularization=500.0):
         self.regularization = regularization
         self.item_weights = None
@@ -78,7 +80,7 @@ class EASE(RecommenderBase):
 
     def _items(self):
         if self.item_weights is None:
-            raise ValueError("EASE: the model has not been fitted")
+            raise ValueError(f"{self._name}: the model has not been fitted")
         return self.item_weights.shape[0]
 
     def _topk(self, rows, N, filter_liked, filter_items, items):
@@ -163,7 +165,7 @@ class EASE(RecommenderBase):
         return ids, scores
 
     def similar_users(self, userid, N=10, filter_users=None, users=None):
-        raise NotImplementedError("similar_users isn't implemented for EASE: the model has no user representation")
+        raise NotImplementedError(f"similar_users isn't implemented for {self._name}: the model has no user representation")
 
     # ---- persistence -------------------------------------------------------------------------------------------------------
     def __getstate__(self):

@@ -13,7 +13,8 @@ try:
     from ._cuda import (COOMatrix, Comm, CSRMatrix, IntVector, IVFIndex, KnnQuery, LeastSquaresSolver, Matrix,  # noqa: F401
                         Profiler, RandomState, RankingMetrics, SpMat, bpr_epoch, bpr_update, calculate_norms, core_clock_mhz, debug_occupy, fixup_rows, get_device, get_device_count, get_oversubscribe, host_ranking_metrics, lmf_update, release_workspaces,
                         set_deferred_sync, set_device, set_oversubscribe, sparse_topk_product, synchronize, warp_epoch,
-                        ease_gram, ease_topk, ease_weights, mem_get_info, multiply_small, spd_inverse, spmm)
+                        ease_gram, ease_topk, ease_weights, mem_get_info, multiply_small, slim_solve, slim_stats, slim_workspace_bytes, SLIM_MAX_ITEMS,
+                        spd_inverse, spmm)
     from ._rsvd import randomized_svd  # noqa: F401
     from ._hip import lib as _lib
 

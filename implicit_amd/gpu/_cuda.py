@@ -10,8 +10,8 @@ NEW relative to the reference: LeastSquaresSolver.least_squares_cholesky (the re
 has no Cholesky solver), the Comm class (RCCL exchange for the multi-GPU fit), lmf_update (the
 reference has no GPU LMF), SpMat / sparse_topk_product (the reference's nearest-neighbour models are CPU only), IVFIndex
 (a native IVF-Flat index in place of the faiss one the reference's ann wrappers build) and ease_gram / spd_inverse /
-ease_weights / ease_topk (the EASE model, which the reference does not have), and spmm / multiply_small (the products of
-the randomized SVD behind PureSVD, which the reference does not have either).
+ease_weights / ease_topk (the EASE model, which the reference does not have), slim_solve (the SLIM model, likewise), and
+spmm / multiply_small (the products of the randomized SVD behind PureSVD, which the reference does not have either).
 """
 import ctypes
 
@@ -613,6 +613,44 @@ def ease_topk(knn, B, rows, k, filter_liked=False, item_filter=None):
     check(lib().imp_ease_topk(knn._h, B._h, n, _vp(indptr), _vp(indices), _vp(data), k, 1 if filter_liked else 0,
                               item_filter._h if item_filter is not None else None, _vp(ids), _vp(scores)))
     return ids, scores
+
+
+SLIM_MAX_ITEMS = 40000  # IMP_SLIM_MAX_ITEMS: a column's running product has to fit one workgroup's LDS
+
+
+def slim_workspace_bytes(items):
+    """Device bytes imp_slim_solve reserves besides A and W: the diagonal, the column order, the sweep counts, eight words."""
+    return 4 * (3 * int(items) + 8)
+
+
+def slim_solve(A, l1, positive=True, max_sweeps=100, tol=1e-4, W=None):
+    """NEW: the SLIM weights of a Gram matrix (imp_slim_solve, slim.hip).  A: the float32 items x items Matrix ease_gram returns
+    for regularization = l2.  Column j of the result minimises 1/2 w^T A w - sum_i A[j, i] w_i + l1 sum_i |w_i| subject to
+    w_j = 0 (and w >= 0 when `positive`) by cyclic coordinate descent, at most `max_sweeps` sweeps, stopped when the largest
+    change of a sweep is <= tol times the largest weight; defined operation for operation in fp32 (include/implicit_hip.h;
+    tests/slim_reference.py restates it in numpy).  Returns (W, sweeps): W a float32 items x items Matrix in the layout of
+    EASE's B (W[i, j] = weight of source i for target j, zero diagonal; `W`: a Matrix to write into, default a new one), sweeps
+    an int32 array of the sweeps each column ran.  At most 40 000 items.  Arguments the library refuses raise ValueError with
+    W untouched; a diagonal entry of A that is not finite or not > 0 names the smallest such item."""
+    if not isinstance(A, Matrix):
+        raise TypeError("slim_solve: A must be an implicit_amd.gpu.Matrix")
+    if W is None:
+        if A.shape[0] > SLIM_MAX_ITEMS:
+            raise ValueError(f"slim_solve: {A.shape[0]} items, at most {SLIM_MAX_ITEMS} are supported")
+        W = Matrix.zeros(A.shape[0], A.shape[0])
+    elif not isinstance(W, Matrix):
+        raise TypeError("slim_solve: W must be an implicit_amd.gpu.Matrix")
+    sweeps = np.zeros(A.shape[0], dtype=np.int32)
+    check(lib().imp_slim_solve(A._h, float(l1), 1 if positive else 0, int(max_sweeps), float(tol), W._h, _vp(sweeps)))
+    return W, sweeps
+
+
+def slim_stats():
+    """Measurement aid (imp_slim_stats): (updates applied by the last slim_solve on this device, the longest time one column held
+    its workgroup in seconds)."""
+    updates, longest = ctypes.c_ulonglong(0), ctypes.c_double(0.0)
+    check(lib().imp_slim_stats(ctypes.byref(updates), ctypes.byref(longest)))
+    return int(updates.value), float(longest.value)
 
 
 def spmm(csr, dense, out=None):

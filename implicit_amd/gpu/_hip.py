@@ -133,6 +133,8 @@ _SIGNATURES = {
     "imp_ease_weights": [ctypes.c_void_p],
     "imp_ease_topk": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    "imp_slim_solve": [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p],
+    "imp_slim_stats": [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_double)],
     "imp_csr_spmm": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     "imp_matrix_multiply_small": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     "imp_comm_unique_id": [ctypes.c_void_p],

@@ -426,6 +426,35 @@ int imp_ease_topk(imp_knn *k, const imp_matrix *B, int32_t rows, const int64_t *
                   const float *data, int topk, int filter_liked, const imp_intvector *item_filter, int32_t *ids,
                   float *scores);
 
+/* ---- NEW: SLIM, the elastic-net item-item model (Ning & Karypis, ICDM 2011; no reference counterpart; csrc/slim.hip,
+ * DESIGN 4.20): `items` independent problems in Gram form, solved by cyclic coordinate descent.  No floating-point atomics:
+ * equal inputs give bitwise equal outputs, whatever ran before.  The call is synchronous. ------------------------------------ */
+#define IMP_SLIM_MAX_ITEMS 40000 /* one workgroup keeps a column's running product (items floats) in its 160 KiB of LDS */
+/* A: fp32 items x items, symmetric, what imp_ease_gram(.., regularization = l2) returns.  W (caller-allocated fp32, items x
+ * items; its contents on entry do not matter): W[i][j] = the weight of source item i for target j, the layout of EASE's B, so
+ * imp_ease_topk serves it; W[j][j] = +0.  Column j minimises  1/2 w^T A w - sum_i A[j][i] w_i + l1 sum_i |w_i|  subject to
+ * w_j = 0 (and w >= 0 when `positive`), by this rule, every operation a separately rounded fp32 operation:
+ *   w = 0, r = 0 (items floats each); for sweep s = 1 .. max_sweeps:
+ *     dmax = 0; for i = 0 .. items - 1 ascending, i != j:
+ *       a = A[i][i];  rho = (A[j][i] - r[i]) + a w[i]
+ *       positive:  t = rho - l1;  new = t > 0 ? t / a : +0
+ *       otherwise: new = rho > l1 ? (rho - l1) / a : rho < -l1 ? (rho + l1) / a : +0
+ *       d = new - w[i];  if d != 0:  w[i] = new;  r[k] = r[k] + d A[i][k] for every k;  dmax = max(dmax, |d|)
+ *     wmax = max_k |w[k]|;  the column stops when dmax <= tol wmax (a sweep that changed nothing stops it whatever tol is)
+ *   sweeps[j] (HOST, items entries, nullable) = the number of sweeps column j ran.
+ * r is never recomputed from w: its rounding accumulates, so tol = 0 means "exactly max_sweeps sweeps unless a sweep changes
+ * nothing" (DESIGN 4.20).  Workspace: 3 items + 8 four-byte words, kept for the next call (imp_release_workspaces).
+ * IMP_INVALID_ARGUMENT with W untouched: a NULL A or W, matrices that are not square fp32 of one order, A and W sharing
+ * storage, l1 or tol negative or not finite, max_sweeps < 1, items > IMP_SLIM_MAX_ITEMS (the call is refused, not routed to a
+ * slower kernel), a diagonal entry of A that is not finite or not > 0 (checked by a kernel before anything is written; the
+ * message names the smallest such item).  items = 0 succeeds and does nothing. */
+int imp_slim_solve(const imp_matrix *A, float l1, int positive, int max_sweeps, float tol, imp_matrix *W, int32_t *sweeps);
+/* Measurement aid for profiles/slim_bench.py, NOT part of the model's contract (like imp_debug_occupy and imp_debug_core_clock:
+ * no model or shim path depends on it, and it may change with the kernel): what the last imp_slim_solve on this device
+ * counted -- the updates it applied (coordinates with d != 0, all columns) and the longest time one column held its
+ * workgroup, in seconds. */
+int imp_slim_stats(unsigned long long *updates, double *longest_column_seconds);
+
 /* ---- NEW: the two products of the randomized truncated SVD behind PureSVD (Cremonesi, Koren, Turrin 2010; Halko,
  * Martinsson, Tropp 2011; no reference counterpart; csrc/svd.hip).  No floating-point atomics: equal inputs give
  * bitwise equal outputs.  Both calls are synchronous and read no row schedule but A's. --------------------------------------- */
