@@ -661,34 +661,34 @@ bool cg_native_half(int f) { return f == 64 || f == 128; }
 // The padded copy of Y is kept for the next call against the same matrix (the row chunks of a sharded sweep).
 static void least_squares_cg_padded(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, int cg_steps, int F) {
   const size_t rx = (size_t)C->rows;
-  const PaddedViews p = pad_in(X, Y, YtY, rx, F, true);
-  if (F == 64) cg_f64_f128<1, float>(C, p.X.f32(), p.Y.f32(), p.Y.rows, p.YtY.f32(), cg_steps);
-  else if (F == 128) cg_f64_f128<2, float>(C, p.X.f32(), p.Y.f32(), p.Y.rows, p.YtY.f32(), cg_steps);
-  else cg_f256(C, p.X.f32(), p.Y.f32(), p.YtY.f32(), cg_steps);
+  PaddedViews p = pad_in(X, Y, YtY, rx, F, true);
+  float *x = p.X.mut<float>();
+  if (F == 64) cg_f64_f128<1, float>(C, x, p.Y.f32(), p.Y.rows, p.YtY.f32(), cg_steps);
+  else if (F == 128) cg_f64_f128<2, float>(C, x, p.Y.f32(), p.Y.rows, p.YtY.f32(), cg_steps);
+  else cg_f256(C, x, p.Y.f32(), p.YtY.f32(), cg_steps);
   pad_out(X, rx, F);
 }
 
 void least_squares_cg(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, int cg_steps) {
-  note_device_write(X->data, (size_t)C->rows * X->cols * X->itemsize);  // the rows this call solves
   // one event pair around ALL launches of the half sweep (every row class): what bench.py's whole-step `roofline` is timed on
   IMP_PROF("als_cg_half_sweep");
   const int f = (int)X->cols;
   const float *a0 = YtY->f32();
   if (X->itemsize == 2) {
     if (!cg_native_half(f)) throw std::invalid_argument("least_squares: fp16 factors with this factor count are converted by the caller");
-    __half *x = reinterpret_cast<__half *>(X->data);
-    const __half *y = reinterpret_cast<const __half *>(Y->data);
+    __half *x = X->mut_rows<__half>(0, (size_t)C->rows);
+    const __half *y = Y->as<__half>();
     if (f == 64) cg_f64_f128<1, __half>(C, x, y, Y->rows, a0, cg_steps);
     else cg_f64_f128<2, __half>(C, x, y, Y->rows, a0, cg_steps);
     return;
   }
-  float *x = X->f32();
-  const float *y = Y->f32();
   // IMP_NO_PAD=1: factor counts other than 64 / 128 / 256 on the generic kernels (A/B, parity)
   if (solver_switches().cg_pad && f < 256 && f != 64 && f != 128 && f >= 1) {  // 129 .. 255 (the reference publishes f = 192) ride the f = 256 kernels
     least_squares_cg_padded(C, X, YtY, Y, cg_steps, f < 64 ? 64 : (f < 128 ? 128 : 256));
     return;
   }
+  float *x = X->mut_rows<float>(0, (size_t)C->rows);  // the rows this call solves
+  const float *y = Y->f32();
   if (f == 64) cg_f64_f128<1, float>(C, x, y, Y->rows, a0, cg_steps);
   else if (f == 128) cg_f64_f128<2, float>(C, x, y, Y->rows, a0, cg_steps);
   else if (f == 256) cg_f256(C, x, y, a0, cg_steps);

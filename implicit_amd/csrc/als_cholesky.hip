@@ -719,6 +719,7 @@ __global__ __launch_bounds__(256, 3) void als_cholesky_f64_kernel(const int32_t 
 
 // f = 64: every non-empty row (there is one): MFMA A-build + left-looking Cholesky, one wavefront per row
 static int64_t cholesky_f64(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg) {
+  float *const x = X->mut_rows<float>(0, (size_t)C->rows);  // the rows this call solves
   unsigned long long *g_failed = reset_fail_word();
   const int nonempty = C->nonempty();
   const size_t lds_m = ((size_t)64 * 68 + 4 * kCholTri) * sizeof(float);  // 52 KB: 3 workgroups per CU
@@ -740,17 +741,18 @@ static int64_t cholesky_f64(const imp_csr *C, imp_matrix *X, const imp_matrix *Y
     allow_dynamic_lds(als_cholesky_f64_kernel<false>, lds_m);
     IMP_PROF("als_cholesky_mfma_rows");
     als_cholesky_f64_kernel<false><<<grid, 256, lds_m, stream()>>>(C->order.data(), 0, nonempty, C->indptr.data(), C->indices.data(),
-                                                                   C->data.data(), X->f32(), Y->f32(), YtY->f32(), (float)reg,
+                                                                   C->data.data(), x, Y->f32(), YtY->f32(), (float)reg,
                                                                    g_failed, nullptr, plan, partials);
     IMP_CHECK_HIP(hipGetLastError());
   }
-  zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), 64);
+  zero_rows(C->order.data(), C->first_empty(), C->n_empty(), x, 64);
   return read_fail_word(g_failed);
 }
 
 // any other f: the normal-matrix path at f = 128, the wave kernels for the short rows at f <= 64, the workgroup kernel for the rest
 static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg) {
   const int f = (int)X->cols;
+  float *const x = X->mut_rows<float>(0, (size_t)C->rows);  // the rows this call solves
   unsigned long long *g_failed = reset_fail_word();
   const int nonempty = C->nonempty();
   // f = 128 (round 5): the rows' normal matrices on the matrix cores, factorised on their LDS images (als_cg_nm.hip); the
@@ -758,7 +760,7 @@ static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matri
   // IMP_CHOL_NM=0: every row on the workgroup kernel (A/B, parity)
   CholNmList nm_list{nullptr, nullptr, 0};
   const bool use_nm = f == 128 && solver_switches().chol_nm && nonempty > 0;
-  if (use_nm) nm_list = least_squares_cholesky_nm(C, X->f32(), Y->f32(), Y->rows, YtY->f32(), (float)reg);
+  if (use_nm) nm_list = least_squares_cholesky_nm(C, x, Y->f32(), Y->rows, YtY->f32(), (float)reg);
   // other f <= 64: rows up to 256 nnz go to the register-resident wave kernel; longer rows (and any larger f) to the
   // workgroup kernel, whose 256 threads share the A-build of one row
   const int n_block = f <= 64 ? C->bin_start[2] : nonempty;
@@ -767,7 +769,7 @@ static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matri
     int grid = std::min((n_wave + 3) / 4, ctx().num_cus * 8);
     IMP_PROF("als_cholesky_wave_rows");
     auto kern = f <= 32 ? als_cholesky_wave_kernel<32> : als_cholesky_wave_kernel<64>;
-    kern<<<grid, 256, 0, stream()>>>(C->order.data(), n_block, n_wave, C->indptr.data(), C->indices.data(), C->data.data(), X->f32(),
+    kern<<<grid, 256, 0, stream()>>>(C->order.data(), n_block, n_wave, C->indptr.data(), C->indices.data(), C->data.data(), x,
                                      Y->f32(), YtY->f32(), f, (float)reg, g_failed);
     IMP_CHECK_HIP(hipGetLastError());
   }
@@ -784,7 +786,7 @@ static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matri
       IMP_PROF("als_cholesky_rows");
       auto kern = als_cholesky_blocked_kernel<false, true, 17, 16>;
       allow_dynamic_lds(kern, lds);
-      kern<<<grid, 256, lds, stream()>>>(C->order.data(), 0, n_block, C->indptr.data(), C->indices.data(), C->data.data(), X->f32(),
+      kern<<<grid, 256, lds, stream()>>>(C->order.data(), 0, n_block, C->indptr.data(), C->indices.data(), C->data.data(), x,
                                          Y->f32(), YtY->f32(), f, (float)reg, lda, g_failed, 0, nullptr, ws);
       IMP_CHECK_HIP(hipGetLastError());
     } else {
@@ -803,14 +805,14 @@ static int64_t cholesky_general(const imp_csr *C, imp_matrix *X, const imp_matri
       if (use_nm)  // the listed rows only (the list stands in for the schedule; a zero count makes every workgroup return at once)
         kern<<<std::min(nm_list.capacity, ctx().num_cus * per_cu), 256, lds, stream()>>>(
             reinterpret_cast<const int32_t *>(nm_list.rows), 0, nm_list.capacity, C->indptr.data(), C->indices.data(), C->data.data(),
-            X->f32(), Y->f32(), YtY->f32(), f, (float)reg, lda, g_failed, ko, nm_list.count, nullptr);
+            x, Y->f32(), YtY->f32(), f, (float)reg, lda, g_failed, ko, nm_list.count, nullptr);
       else
-        kern<<<grid, 256, lds, stream()>>>(C->order.data(), 0, n_block, C->indptr.data(), C->indices.data(), C->data.data(), X->f32(),
+        kern<<<grid, 256, lds, stream()>>>(C->order.data(), 0, n_block, C->indptr.data(), C->indices.data(), C->data.data(), x,
                                            Y->f32(), YtY->f32(), f, (float)reg, lda, g_failed, ko, nullptr, nullptr);
       IMP_CHECK_HIP(hipGetLastError());
     }
   }
-  zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), f);
+  zero_rows(C->order.data(), C->first_empty(), C->n_empty(), x, f);
   return read_fail_word(g_failed);
 }
 

@@ -43,44 +43,39 @@ PaddedViews pad_in(const imp_matrix *X, const imp_matrix *Y, const imp_matrix *Y
   PaddedSystem &p = ctx().pad;
   const size_t rx = rows_of_X, ry = Y->rows;
   p.x.reserve(rx * F);
-  // no copy is kept of memory whose writes the library does not see -- wrapped foreign memory, a matrix whose address was handed
-  // out (the predicate of the cached item planes, topk.hip)
-  if (!(Y->storage && Y->storage->owned && !Y->storage->exposed)) reuse_y = false;
   // a copy that may not be re-used, or that goes with its buffer, is forgotten (before the reserve: freeing the buffer reports a
   // write to that memory)
-  if (!reuse_y || p.y.size < ry * F) p.forget_y();
+  if (!reuse_y || p.y.size < ry * F) p.y_key.drop();
   p.y.reserve(ry * F);
   p.gram.reserve((size_t)F * F);
   {
     IMP_PROF("pad_factors");
     // The padded copy of Y is re-used when this call solves against the SAME matrix under the SAME gramian as the previous
-    // one -- the K row chunks of a sharded half sweep (4 redundant copies of a 10 M-row replica otherwise).  Same address, shape
-    // and factor counts are checked here; "same contents" is decided on the device, with no host wait, through the gramian:
+    // one -- the K row chunks of a sharded half sweep (4 redundant copies of a 10 M-row replica otherwise).  Same memory, not
+    // written through the library since (y_key), shape and factor counts are checked here; "same contents" is decided on the
+    // device, with no host wait, through the gramian:
     // whoever changes Y recomputes YtY (the solve is meaningless otherwise), so a gramian equal bit for bit to the one the copy
     // was made under vouches for it.  The flag is read by the pad kernel itself, which then returns at once.
     const int *skip = nullptr;
-    if (ry && p.y_src == Y->data && p.y_rows == ry && p.y_f == f && p.y_F == F) {
+    if (ry && p.y_key.made_from(Y) && p.y_rows == ry && p.y_f == f && p.y_F == F) {
       IMP_PROF_NESTED("padded_y_check");  // one count per call that found a kept copy to vouch for: what the cache tests read
       skip = p.same.reserve(1);
       pad_check_kernel<<<1, 1024, 0, stream()>>>(YtY->f32(), p.gram.data(), f, F, p.same.data());
     }
     if (ry) pad_rows(pad_grid(ry * F), Y->f32(), p.y.data(), ry, f, F, skip);
-    if (reuse_y) p.y_src = Y->data, p.y_rows = ry, p.y_f = f, p.y_F = F;
+    // (no copy is kept of memory whose writes the library does not see: binding to such a matrix binds to nothing)
+    if (reuse_y) p.y_key.bind(Y), p.y_rows = ry, p.y_f = f, p.y_F = F;
     if (rx) pad_rows(pad_grid(rx * F), X->f32(), p.x.data(), rx, f, F);
     pad_gram_kernel<<<pad_grid((size_t)F * F), 256, 0, stream()>>>(YtY->f32(), p.gram.data(), f, F);
     IMP_CHECK_HIP(hipGetLastError());
   }
-  PaddedViews v;
-  v.X.rows = rx, v.X.cols = F, v.X.data = p.x.data();
-  v.Y.rows = ry, v.Y.cols = F, v.Y.data = p.y.data();
-  v.YtY.rows = F, v.YtY.cols = F, v.YtY.data = p.gram.data();
-  return v;
+  return {imp_matrix(rx, F, 4, p.x.storage), imp_matrix(ry, F, 4, p.y.storage), imp_matrix(F, F, 4, p.gram.storage)};
 }
 
 void pad_out(imp_matrix *X, size_t rows_of_X, int F) {
   const int f = (int)X->cols;
   IMP_PROF("unpad_factors");
-  if (rows_of_X) unpad_rows_kernel<<<pad_grid(rows_of_X * f), 256, 0, stream()>>>(ctx().pad.x.data(), X->f32(), rows_of_X, f, F);
+  if (rows_of_X) unpad_rows_kernel<<<pad_grid(rows_of_X * f), 256, 0, stream()>>>(ctx().pad.x.data(), X->mut_rows<float>(0, rows_of_X), rows_of_X, f, F);
   IMP_CHECK_HIP(hipGetLastError());
 }
 

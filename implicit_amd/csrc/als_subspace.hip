@@ -348,14 +348,15 @@ static void subspace_launch(const imp_csr *C, float *X, const float *G, const fl
 int64_t least_squares_subspace(const imp_csr *C, imp_matrix *X, const imp_matrix *YtY, const imp_matrix *Y, double reg, int block_size,
                                int sweeps) {
   const int f = (int)X->cols;
+  float *const x = X->mut_rows<float>(0, (size_t)C->rows);  // the rows this call solves
   unsigned long long *g_failed = reset_fail_word();
   if (C->nonempty() > 0) {
     float *pred = ctx().subspace_pred.reserve((size_t)C->nnz);
-    if (block_size <= 8) subspace_launch<8>(C, X->f32(), YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
-    else if (block_size <= 16) subspace_launch<16>(C, X->f32(), YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
-    else subspace_launch<32>(C, X->f32(), YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
+    if (block_size <= 8) subspace_launch<8>(C, x, YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
+    else if (block_size <= 16) subspace_launch<16>(C, x, YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
+    else subspace_launch<32>(C, x, YtY->f32(), Y->f32(), pred, f, (float)reg, block_size, sweeps, g_failed);
   }
-  zero_rows(C->order.data(), C->first_empty(), C->n_empty(), X->f32(), f);
+  zero_rows(C->order.data(), C->first_empty(), C->n_empty(), x, f);
   return read_fail_word(g_failed);
 }
 

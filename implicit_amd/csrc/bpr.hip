@@ -127,7 +127,7 @@ extern "C" int imp_bpr_update(const imp_intvector *userids, const imp_intvector 
   return guarded([&] {
     pair_update("bpr_update", "bpr_check_ids", "bpr_update", userids, itemids, indptr, X, Y, samples, correct, skipped,
                 [&](int G, int grid, int64_t n, unsigned long long *stats) {
-                  const BprArgs a{userids->v.data(), itemids->v.data(), indptr->v.data(), X->f32(), Y->f32(), (int64_t)userids->size, n,
+                  const BprArgs a{userids->v.data(), itemids->v.data(), indptr->v.data(), X->mut<float>(), Y->mut<float>(), (int64_t)userids->size, n,
                                   (uint64_t)seed, learning_rate, regularization, (int)X->cols, verify_negative ? 1 : 0, stats};
                   for_group_shape<false>(G, a.C, [&](auto g, auto cpl) {
                     bpr_update_kernel<decltype(g)::value, decltype(cpl)::value><<<grid, 256, 0, stream()>>>(a);

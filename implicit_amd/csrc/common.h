@@ -12,6 +12,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/implicit_hip.h"
@@ -164,23 +165,39 @@ template <typename T> struct DeviceArray {
     if (n) IMP_CHECK_HIP(hipMemcpyAsync(data(), host, n * sizeof(T), hipMemcpyHostToDevice, stream()));
   }
 };
+// a C-ABI entry point is about to write `bytes` at `dst` through the library (or the memory is being freed, or its address is
+// leaving the library): whatever a registered DerivedCache was made from memory the range overlaps is dropped -- wherever the
+// cache lives (device addresses are unique across the devices of a process; a Storage may die on a thread whose current device
+// is not the one that holds the cache).  Called by the write accessors of imp_matrix below, never by an entry point itself.
+void note_device_write(const void *dst, size_t bytes);
+// Something derived from a matrix and kept across calls (the fragment-ordered fp16 planes of an item matrix in a KnnQuery
+// handle, topk.hip; the zero-padded copy of Y, PaddedSystem), named by the memory it was made from.  Holds for memory only
+// the library writes: a Storage whose address was handed out (imp_matrix_device_ptr) or that wraps foreign memory
+// (imp_matrix_wrap_device) is never bound to.  The key is only touched under the lock note_device_write takes (containers.hip).
+struct DerivedCache {
+  void bind(const imp_matrix *m);             // made from m as it is now; from nothing when the library cannot vouch for m's memory
+  bool made_from(const imp_matrix *m) const;  // bound to m's address and size, not written since, and m still vouched for
+  void drop();
+
+ private:
+  friend void note_device_write(const void *, size_t);
+  const void *src = nullptr;
+  size_t bytes = 0;
+};
+void register_derived_cache(DerivedCache *c);
+void unregister_derived_cache(DerivedCache *c);
+
 // Workspaces of a zero-padded half sweep (als_pad.hip): X, Y and the gramian with F >= f columns, and which matrix `y` is a
 // padded copy of -- the chunks of a sharded CG half sweep solve against the same Y, one padded copy serves them all.
 struct PaddedSystem {
   DeviceArray<float> x, y, gram;
   DeviceArray<int> same;  // device flag: the gramian of this call equals the one `y` was made under
-  const void *y_src = nullptr;
+  DerivedCache y_key;     // registered with its context (ctx())
   size_t y_rows = 0;
   int y_f = 0, y_F = 0;
-  void forget_y() { y_src = nullptr; }
-  // the copy was made from memory that [dst, dst + bytes) overlaps
-  bool y_made_from(const void *dst, size_t bytes) const {
-    const char *a = static_cast<const char *>(dst), *b = static_cast<const char *>(y_src);
-    return b && a < b + y_rows * (size_t)y_f * sizeof(float) && b < a + bytes;
-  }
   void release() {
+    y_key.drop();
     x = {}, y = {}, gram = {};
-    forget_y();
   }
 };
 
@@ -264,34 +281,53 @@ std::unique_ptr<imp_matrix> astype(const imp_matrix *src, size_t itemsize);    /
 template <typename T> void pad_rows(int grid, const T *src, float *dst, size_t rows, int f, int F, const int *skip = nullptr);
 // als_cg.hip
 void zero_rows(const int32_t *order, int first, int count, float *X, int f);
-// a C-ABI entry point is about to write `bytes` at `dst` through the library (or the memory is being freed): a padded copy of Y
-// made from memory it overlaps (PaddedSystem) is no longer to be trusted -- on WHICHEVER device's context the copy
-// lives (device addresses are unique across the devices of a process; a Storage may die on a thread whose current device is
-// not the one that made the copy).  containers.hip.
-void note_device_write(const void *dst, size_t bytes);
-// Something derived from device memory the library owns and kept across calls (the fragment-ordered fp16 planes of an item
-// matrix in a KnnQuery handle, topk.hip): `src` / `bytes` name what it was made from; note_device_write clears `src` of every
-// registered cache the written range overlaps.  Holds for memory only the library writes: a Storage whose address was handed
-// out (imp_matrix_device_ptr) or that wraps foreign memory (imp_matrix_wrap_device) is never cached from: handing the address
-// out counts as a write, and neither a cache hit nor a kept padded copy of Y is taken from such memory afterwards.
-struct DerivedCache {
-  const void *src = nullptr;
-  size_t bytes = 0;
-};
-void register_derived_cache(DerivedCache *c);
-void unregister_derived_cache(DerivedCache *c);
-
 }  // namespace imp
 
 // ---- handle definitions (opaque in the public header) -------------------------------------------
+// The device pointer is private: reading gives const pointers, and the only way to a mutable one is an accessor that reports
+// the write (note_device_write) for exactly the bytes it hands out -- nothing derived from the matrix outlives a write to it.
 struct imp_matrix {
   size_t rows = 0, cols = 0, itemsize = 4;
-  void *data = nullptr;  // may point inside storage (views)
   std::shared_ptr<imp::Storage> storage;
+  imp_matrix() = default;
+  imp_matrix(size_t rows_, size_t cols_, size_t itemsize_, std::shared_ptr<imp::Storage> s)
+      : rows(rows_), cols(cols_), itemsize(itemsize_), storage(std::move(s)), data(storage ? storage->ptr : nullptr) {}
   size_t bytes() const { return rows * cols * itemsize; }
-  float *f32() const {
+  template <typename T = void> const T *as() const { return static_cast<const T *>(data); }
+  const float *f32() const { return check_f32(), as<float>(); }
+  // rows [first, first + count), about to be written
+  template <typename T = void> T *mut_rows(size_t first, size_t count) {
+    if (std::is_same<T, float>::value) check_f32();
+    char *p = static_cast<char *>(data) + first * cols * itemsize;
+    imp::note_device_write(p, count * cols * itemsize);
+    return reinterpret_cast<T *>(p);
+  }
+  template <typename T = void> T *mut() { return mut_rows<T>(0, rows); }
+  // rows [first, first + count) as a matrix of their own that shares the storage; const of a const matrix
+  imp_matrix rows_view(size_t first, size_t count) { return view(*this, first, count); }
+  const imp_matrix rows_view(size_t first, size_t count) const { return view(*this, first, count); }
+  bool overlaps(const imp_matrix *o) const {  // the two share device memory
+    const char *a = as<char>(), *b = o->as<char>();
+    return bytes() && o->bytes() && a < b + o->bytes() && b < a + bytes();
+  }
+  // imp_matrix_device_ptr: whoever holds the address may write through it -- nothing derived from this memory is cached from
+  // now on, and what was derived from it before is dropped
+  void *expose() const {
+    if (storage) storage->exposed = true;
+    imp::note_device_write(data, bytes());
+    return data;
+  }
+
+ private:
+  void *data = nullptr;  // may point inside storage (views)
+  void check_f32() const {
     if (itemsize != 4) throw std::runtime_error("can't cast Matrix to float*");
-    return reinterpret_cast<float *>(data);
+  }
+  static imp_matrix view(const imp_matrix &m, size_t first, size_t count) {
+    imp_matrix v = m;
+    v.rows = count;
+    v.data = static_cast<char *>(m.data) + first * m.cols * m.itemsize;
+    return v;
   }
 };
 

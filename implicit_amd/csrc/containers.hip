@@ -23,6 +23,7 @@ void set_last_error(const std::string &msg) { g_last_error = msg; }
 static std::mutex g_ctx_mutex;
 // leaked on purpose: the contexts own device buffers, and static destructors run after the HIP runtime has shut down
 static auto &g_contexts = *new std::map<int, std::unique_ptr<Context>>;
+static auto &g_derived = *new std::vector<DerivedCache *>;  // (leaked like the contexts; guarded by g_ctx_mutex)
 
 Context &ctx() {
   int dev = 0;
@@ -37,12 +38,12 @@ Context &ctx() {
     IMP_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
     c->num_cus = prop.multiProcessorCount;
     if (const char *e = getenv("IMP_OVERSUB")) c->oversub = std::max(1, atoi(e));
+    g_derived.push_back(&c->pad.y_key);  // registered for good: a context is never destroyed
     it = g_contexts.emplace(dev, std::move(c)).first;
   }
   return *it->second;
 }
 
-static auto &g_derived = *new std::vector<DerivedCache *>;  // (leaked like the contexts; guarded by g_ctx_mutex)
 void register_derived_cache(DerivedCache *c) {
   std::lock_guard<std::mutex> lock(g_ctx_mutex);
   g_derived.push_back(c);
@@ -59,10 +60,20 @@ void note_device_write(const void *dst, size_t bytes) {
     const char *b = static_cast<const char *>(d->src);
     if (b && a < b + d->bytes && b < a + bytes) d->src = nullptr;
   }
-  for (auto &kv : g_contexts) {
-    PaddedSystem &pad = kv.second->pad;
-    if (pad.y_made_from(dst, bytes)) pad.forget_y();
-  }
+}
+// the one place that decides which memory the library can vouch for: its own, and only until the address is handed out
+static bool trusted(const imp_matrix *m) { return m->storage && m->storage->owned && !m->storage->exposed; }
+void DerivedCache::bind(const imp_matrix *m) {
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  src = trusted(m) ? m->as() : nullptr, bytes = m->bytes();
+}
+bool DerivedCache::made_from(const imp_matrix *m) const {
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  return src && src == m->as() && bytes == m->bytes() && trusted(m);
+}
+void DerivedCache::drop() {
+  std::lock_guard<std::mutex> lock(g_ctx_mutex);
+  src = nullptr;
 }
 
 std::unique_lock<std::recursive_mutex> lock_device() {
@@ -359,13 +370,7 @@ __global__ void core_clock_kernel(long long ticks, unsigned long long *out) {
 
 imp_matrix *new_matrix(size_t rows, size_t cols, size_t itemsize, bool zero) {
   if (itemsize != 4 && itemsize != 2) throw std::invalid_argument("invalid itemsize for Matrix (must be 2 or 4)");
-  auto m = std::make_unique<imp_matrix>();
-  m->rows = rows;
-  m->cols = cols;
-  m->itemsize = itemsize;
-  m->storage = std::make_shared<Storage>(rows * cols * itemsize, zero);
-  m->data = m->storage->ptr;
-  return m.release();
+  return new imp_matrix(rows, cols, itemsize, std::make_shared<Storage>(rows * cols * itemsize, zero));
 }
 
 std::unique_ptr<imp_matrix> astype(const imp_matrix *src, size_t itemsize) {
@@ -373,13 +378,13 @@ std::unique_ptr<imp_matrix> astype(const imp_matrix *src, size_t itemsize) {
   size_t n = src->rows * src->cols;
   if (n) {
     if (itemsize == src->itemsize) {
-      IMP_CHECK_HIP(hipMemcpyAsync(m->data, src->data, src->bytes(), hipMemcpyDeviceToDevice, stream()));
+      IMP_CHECK_HIP(hipMemcpyAsync(m->mut(), src->as(), src->bytes(), hipMemcpyDeviceToDevice, stream()));
     } else if (itemsize == 2) {
       IMP_PROF("cast_f32_f16");
-      cast_f32_f16_kernel<<<grid_for(n), 256, 0, stream()>>>((const float *)src->data, (__half *)m->data, n);
+      cast_f32_f16_kernel<<<grid_for(n), 256, 0, stream()>>>(src->as<float>(), m->mut<__half>(), n);
     } else {
       IMP_PROF("cast_f16_f32");
-      cast_f16_f32_kernel<<<grid_for(n), 256, 0, stream()>>>((const __half *)src->data, (float *)m->data, n);
+      cast_f16_f32_kernel<<<grid_for(n), 256, 0, stream()>>>(src->as<__half>(), m->mut<float>(), n);
     }
     IMP_CHECK_HIP(hipGetLastError());
   }
@@ -703,7 +708,7 @@ int imp_matrix_create(size_t rows, size_t cols, const void *host_data, size_t it
     imp_matrix *m = new_matrix(rows, cols, itemsize, host_data == nullptr);
     std::unique_ptr<imp_matrix> guard(m);
     if (host_data && m->bytes()) {
-      IMP_CHECK_HIP(hipMemcpyAsync(m->data, host_data, m->bytes(), hipMemcpyHostToDevice, stream()));
+      IMP_CHECK_HIP(hipMemcpyAsync(m->mut(), host_data, m->bytes(), hipMemcpyHostToDevice, stream()));
     }
     sync();
     *out = guard.release();
@@ -713,23 +718,14 @@ int imp_matrix_create(size_t rows, size_t cols, const void *host_data, size_t it
 int imp_matrix_wrap_device(size_t rows, size_t cols, void *device_ptr, size_t itemsize, imp_matrix **out) {
   return guarded([&] {
     if (itemsize != 4 && itemsize != 2) throw std::invalid_argument("invalid itemsize for Matrix (must be 2 or 4)");
-    auto m = std::make_unique<imp_matrix>();
-    m->rows = rows;
-    m->cols = cols;
-    m->itemsize = itemsize;
-    m->storage = std::make_shared<Storage>(device_ptr);
-    m->data = device_ptr;
-    *out = m.release();
+    *out = new imp_matrix(rows, cols, itemsize, std::make_shared<Storage>(device_ptr));
   });
 }
 
 int imp_matrix_row(const imp_matrix *src, size_t rowid, imp_matrix **out) {
   return guarded([&] {
     if (rowid >= src->rows) throw std::invalid_argument("row index out of bounds for matrix");
-    auto m = std::make_unique<imp_matrix>(*src);
-    m->rows = 1;
-    m->data = reinterpret_cast<char *>(src->data) + rowid * src->cols * src->itemsize;
-    *out = m.release();
+    *out = new imp_matrix(src->rows_view(rowid, 1));  // the C ABI's views are handles of their own: constness ends here
   });
 }
 
@@ -737,10 +733,7 @@ int imp_matrix_slice(const imp_matrix *src, size_t start, size_t end, imp_matrix
   return guarded([&] {
     if (end < start) throw std::invalid_argument("end_rowid < start_rowid for matrix slice");
     if (end > src->rows) throw std::invalid_argument("row index out of bounds for matrix");
-    auto m = std::make_unique<imp_matrix>(*src);
-    m->rows = end - start;
-    m->data = reinterpret_cast<char *>(src->data) + start * src->cols * src->itemsize;
-    *out = m.release();
+    *out = new imp_matrix(src->rows_view(start, end - start));
   });
 }
 
@@ -752,10 +745,10 @@ int imp_matrix_gather(const imp_matrix *src, const imp_intvector *rowids, imp_ma
       IMP_PROF("gather_rows");
       if (src->itemsize == 4)
         gather_rows_kernel<float><<<grid_for(total), 256, 0, stream()>>>(
-            (const float *)src->data, rowids->v.data(), (float *)m->data, m->rows, m->cols);
+            src->as<float>(), rowids->v.data(), m->mut<float>(), m->rows, m->cols);
       else
         gather_rows_kernel<__half><<<grid_for(total), 256, 0, stream()>>>(
-            (const __half *)src->data, rowids->v.data(), (__half *)m->data, m->rows, m->cols);
+            src->as<__half>(), rowids->v.data(), m->mut<__half>(), m->rows, m->cols);
       IMP_CHECK_HIP(hipGetLastError());
     }
     sync();
@@ -768,11 +761,9 @@ int imp_matrix_resize(imp_matrix *m, size_t rows, size_t cols) {
     if (cols != m->cols) throw std::logic_error("changing number of columns in Matrix::resize is not implemented yet");
     if (rows < m->rows) throw std::logic_error("reducing number of rows in Matrix::resize is not implemented yet");
     auto storage = std::make_shared<Storage>(rows * cols * m->itemsize, true);
-    if (m->bytes()) IMP_CHECK_HIP(hipMemcpyAsync(storage->ptr, m->data, m->bytes(), hipMemcpyDeviceToDevice, stream()));
+    if (m->bytes()) IMP_CHECK_HIP(hipMemcpyAsync(storage->ptr, m->as(), m->bytes(), hipMemcpyDeviceToDevice, stream()));
     sync();
-    m->storage = storage;
-    m->data = storage->ptr;
-    m->rows = rows;
+    *m = imp_matrix(rows, cols, m->itemsize, storage);
   });
 }
 
@@ -784,15 +775,15 @@ int imp_matrix_assign_rows(imp_matrix *m, const imp_intvector *rowids, const imp
     // model's partial_fit_* stays on the device
     if (other->itemsize != m->itemsize) throw std::invalid_argument("dtype mismatch for Matrix::assign_rows");
     size_t total = other->rows * other->cols;
-    note_device_write(m->data, m->bytes());
+    void *dst = m->mut();
     if (total) {
       IMP_PROF("scatter_rows");
       if (m->itemsize == 4)
-        scatter_rows_kernel<float><<<grid_for(total), 256, 0, stream()>>>(m->f32(), rowids->v.data(), other->f32(), other->rows,
+        scatter_rows_kernel<float><<<grid_for(total), 256, 0, stream()>>>((float *)dst, rowids->v.data(), other->f32(), other->rows,
                                                                           other->cols);
       else
-        scatter_rows_kernel<__half><<<grid_for(total), 256, 0, stream()>>>((__half *)m->data, rowids->v.data(),
-                                                                           (const __half *)other->data, other->rows, other->cols);
+        scatter_rows_kernel<__half><<<grid_for(total), 256, 0, stream()>>>((__half *)dst, rowids->v.data(), other->as<__half>(),
+                                                                           other->rows, other->cols);
       IMP_CHECK_HIP(hipGetLastError());
     }
     sync();
@@ -810,9 +801,9 @@ int imp_matrix_calculate_norms(const imp_matrix *src, imp_matrix **out) {
       IMP_PROF("row_norms");
       int grid = grid_for(src->rows * 64);
       if (src->itemsize == 4)
-        row_norms_kernel<float><<<grid, 256, 0, stream()>>>((const float *)src->data, (float *)m->data, src->rows, src->cols);
+        row_norms_kernel<float><<<grid, 256, 0, stream()>>>(src->as<float>(), m->mut<float>(), src->rows, src->cols);
       else
-        row_norms_kernel<__half><<<grid, 256, 0, stream()>>>((const __half *)src->data, (float *)m->data, src->rows, src->cols);
+        row_norms_kernel<__half><<<grid, 256, 0, stream()>>>(src->as<__half>(), m->mut<float>(), src->rows, src->cols);
       IMP_CHECK_HIP(hipGetLastError());
     }
     sync();
@@ -822,15 +813,15 @@ int imp_matrix_calculate_norms(const imp_matrix *src, imp_matrix **out) {
 
 int imp_matrix_to_host(const imp_matrix *m, void *host_out) {
   return guarded([&] {
-    if (m->bytes()) IMP_CHECK_HIP(hipMemcpyAsync(host_out, m->data, m->bytes(), hipMemcpyDeviceToHost, stream()));
+    if (m->bytes()) IMP_CHECK_HIP(hipMemcpyAsync(host_out, m->as(), m->bytes(), hipMemcpyDeviceToHost, stream()));
     sync();
   });
 }
 
 int imp_matrix_from_host(imp_matrix *m, const void *host_in) {
   return guarded([&] {
-    note_device_write(m->data, m->bytes());
-    if (m->bytes()) IMP_CHECK_HIP(hipMemcpyAsync(m->data, host_in, m->bytes(), hipMemcpyHostToDevice, stream()));
+    void *dst = m->mut();
+    if (m->bytes()) IMP_CHECK_HIP(hipMemcpyAsync(dst, host_in, m->bytes(), hipMemcpyHostToDevice, stream()));
     sync();
   });
 }
@@ -841,11 +832,9 @@ int imp_matrix_copy_rows(imp_matrix *dst, size_t dst_row, const imp_matrix *src,
       throw std::invalid_argument("copy_rows: the two matrices must have rows of the same width and itemsize");
     if (dst_row + rows > dst->rows || src_row + rows > src->rows) throw imp::out_of_range_error("copy_rows: row range out of bounds");
     const size_t row_bytes = dst->cols * dst->itemsize;
-    note_device_write(static_cast<char *>(dst->data) + dst_row * row_bytes, rows * row_bytes);
+    void *to = dst->mut_rows(dst_row, rows);
     if (rows && row_bytes)
-      IMP_CHECK_HIP(hipMemcpyAsync(static_cast<char *>(dst->data) + dst_row * row_bytes,
-                                   static_cast<const char *>(src->data) + src_row * row_bytes, rows * row_bytes,
-                                   hipMemcpyDeviceToDevice, stream()));
+      IMP_CHECK_HIP(hipMemcpyAsync(to, src->as<char>() + src_row * row_bytes, rows * row_bytes, hipMemcpyDeviceToDevice, stream()));
     sync_call();  // queue-only in deferred mode, like the exchange it stands in for
   });
 }
@@ -860,11 +849,7 @@ int imp_matrix_shape(const imp_matrix *m, size_t *rows, size_t *cols, size_t *it
 
 int imp_matrix_device_ptr(const imp_matrix *m, void **ptr) {
   return guarded([&] {
-    *ptr = m->data;
-    // whoever holds the address may write through it: nothing derived from this memory is cached from now on, and what was
-    // derived from it before is dropped
-    if (m->storage) m->storage->exposed = true;
-    note_device_write(m->data, m->bytes());
+    *ptr = m->expose();
   });
 }
 

@@ -262,14 +262,14 @@ extern "C" int imp_ease_gram(const imp_csr *item_users, const imp_csr *user_item
     if (G->itemsize != 4 || G->rows != items || G->cols != items) throw std::invalid_argument("ease_gram: G must be float32, items x items");
     if (items == 0) return;
     IMP_PROF("ease_gram");
-    note_device_write(G->data, G->bytes());
+    float *const g = G->mut<float>();
     allow_dynamic_lds_once<ease_gram_kernel>(kGramSlab * sizeof(float));
     const unsigned slabs = (unsigned)((items + kGramSlab - 1) / kGramSlab);
     ease_gram_kernel<<<dim3((unsigned)items, slabs), 256, kGramSlab * sizeof(float), stream()>>>(
         item_users->indptr.data(), item_users->indices.data(), item_users->data.data(), user_items->indptr.data(),
-        user_items->indices.data(), user_items->data.data(), (int)items, regularization, G->f32());
+        user_items->indices.data(), user_items->data.data(), (int)items, regularization, g);
     IMP_CHECK_HIP(hipGetLastError());
-    mirror_lower(G->f32(), items);
+    mirror_lower(g, items);
     sync();
   });
 }
@@ -292,8 +292,7 @@ extern "C" int imp_ease_weights(imp_matrix *P) {
     IMP_CHECK_HIP(hipMemcpyAsync(&h_bad, bad.data(), sizeof(int), hipMemcpyDeviceToHost, stream()));
     sync();
     if (h_bad) throw std::invalid_argument("ease_weights: a diagonal entry is zero or not finite");
-    note_device_write(P->data, P->bytes());
-    ease_weights_kernel<<<dim3((unsigned)n, (unsigned)((n + 255) / 256)), 256, 0, stream()>>>(P->f32(), (long)n, diag.data());
+    ease_weights_kernel<<<dim3((unsigned)n, (unsigned)((n + 255) / 256)), 256, 0, stream()>>>(P->mut<float>(), (long)n, diag.data());
     IMP_CHECK_HIP(hipGetLastError());
     sync();
   });

@@ -182,7 +182,7 @@ extern "C" int imp_eval_add(imp_eval *e, const imp_matrix *ids, const imp_intvec
     const int64_t tiles = (n + kEvalBlock / G - 1) / (kEvalBlock / G);
     const int grid = (int)std::min<int64_t>(tiles, kEvalMaxGrid);
     const EvalArgs a{e->indptr.data(), e->indices.data(), e->tables.data(), e->tables.data() + e->k,
-                     static_cast<const int32_t *>(ids->data), userids->v.data(), rows_out.data(), e->slots.data(), n,
+                     ids->as<int32_t>(), userids->v.data(), rows_out.data(), e->slots.data(), n,
                      e->rows, e->cols, e->k};
     {
       IMP_PROF("eval_rows");

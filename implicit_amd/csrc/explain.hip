@@ -314,7 +314,7 @@ int64_t explain_factor(const imp_csr *C, const imp_matrix *YtY, const imp_matrix
   {
     IMP_PROF("explain_factor");
     explain_factor_kernel<<<grid, 256, lds, stream()>>>(C->indptr.data(), C->indices.data(), C->data.data(), C->rows, Y->f32(),
-                                                        YtY->f32(), f, (float)reg, weights->f32(), g_failed);
+                                                        YtY->f32(), f, (float)reg, weights->mut<float>(), g_failed);
     IMP_CHECK_HIP(hipGetLastError());
   }
   return read_fail_word(g_failed);
@@ -380,7 +380,6 @@ int imp_solver_explain_factor(imp_solver *, const imp_csr *cui, const imp_matrix
     if (YtY->itemsize != 4) throw std::invalid_argument("explain_factor: YtY must be float32");
     if (YtY->rows != YtY->cols || YtY->cols != Y->cols)
       throw std::invalid_argument("explain_factor: YtY must be square with as many columns as Y");
-    note_device_write(weights->data, weights->bytes());
     const int64_t failed = explain_factor(cui, YtY, Y, regularization, weights);
     if (failed_row) *failed_row = failed;
     if (failed >= 0)

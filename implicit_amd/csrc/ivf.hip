@@ -585,7 +585,7 @@ extern "C" int imp_ivf_build(const imp_matrix *vectors, int nlist, int iteration
 
     DeviceArray<float> vec;
     vec.alloc(n * f_pad);
-    ivf_pad(vectors->data, vectors->itemsize, n, (int)f, f_pad, vec.data());
+    ivf_pad(vectors->as(), vectors->itemsize, n, (int)f, f_pad, vec.data());
     DeviceArray<int32_t> init;
     init.upload(init_rows, nlist);
     ix->centroids.alloc((size_t)nlist * f_pad);
@@ -705,7 +705,7 @@ extern "C" int imp_ivf_search(imp_ivf *ix, const imp_matrix *query, int k, int n
 
     for (size_t q0 = 0; q0 < nq; q0 += chunk) {
       const size_t rows = std::min(chunk, nq - q0);
-      ivf_pad(static_cast<const char *>(query->data) + q0 * ix->f * query->itemsize, query->itemsize, rows, (int)ix->f, f_pad, Q.data());
+      ivf_pad(query->as<char>() + q0 * ix->f * query->itemsize, query->itemsize, rows, (int)ix->f, f_pad, Q.data());
       coarse.dense(Q.data(), (int)rows, ix->centroids.data(), nlist, f_pad, S.data());
       {
         IMP_PROF("ivf_select_probes");

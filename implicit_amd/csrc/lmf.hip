@@ -217,11 +217,6 @@ static void launch_lmf(const LmfArgs &a, LmfPass pass, int64_t work) {
   IMP_CHECK_HIP(hipGetLastError());
 }
 
-static bool overlaps(const imp_matrix *p, const imp_matrix *q) {
-  const char *a = static_cast<const char *>(p->data), *b = static_cast<const char *>(q->data);
-  return p->bytes() && q->bytes() && a < b + q->bytes() && b < a + p->bytes();
-}
-
 }  // namespace imp
 
 using namespace imp;
@@ -242,16 +237,15 @@ extern "C" int imp_lmf_update(const imp_csr *cui, imp_matrix *X, const imp_matri
     const int C = (int)X->cols;
     if (neg_prop < 0) throw std::invalid_argument("lmf_update: neg_prop must be >= 0");
     if (one_col < -1 || one_col >= C) throw std::invalid_argument("lmf_update: one_col must lie in [-1, C)");
-    if (overlaps(X, Y) || overlaps(X, deriv_sum_sq) || overlaps(deriv_sum_sq, Y))
+    if (X->overlaps(Y) || X->overlaps(deriv_sum_sq) || deriv_sum_sq->overlaps(Y))
       throw std::invalid_argument("lmf_update: X, Y and deriv_sum_sq must not share storage");
     if (!cui->parts.empty())
       throw std::invalid_argument("lmf_update: a CSR held in several >2^31-nonzero blocks is not supported");
 
-    note_device_write(X->data, X->bytes());  // cached top-k planes made from X are stale after this
-    note_device_write(deriv_sum_sq->data, deriv_sum_sq->bytes());
+    float *const x = X->mut<float>();  // (cached top-k planes made from X are stale from here on)
     if (cui->nnz > 0) {
       const LongPlan &lp = cui->plan_all;
-      LmfArgs a{cui->indptr.data(), cui->indices.data(), cui->data.data(), cui->order.data(), Y->f32(), X->f32(), deriv_sum_sq->f32(),
+      LmfArgs a{cui->indptr.data(), cui->indices.data(), cui->data.data(), cui->order.data(), Y->f32(), x, deriv_sum_sq->mut<float>(),
                 nullptr, lp.dev(cui->order.data()), cui->nnz, cui->bin_start[1], cui->bin_start[imp_csr::kBins - 1], (uint64_t)seed,
                 learning_rate, regularization, C, neg_prop};
       if (lp.n_seg > 0) {
@@ -270,7 +264,7 @@ extern "C" int imp_lmf_update(const imp_csr *cui, imp_matrix *X, const imp_matri
     }
     if (one_col >= 0 && X->rows > 0) {
       const int grid = (int)std::min<int64_t>(((int64_t)X->rows + 255) / 256, (int64_t)ctx().num_cus * 4);
-      lmf_one_col_kernel<<<grid, 256, 0, stream()>>>(X->f32(), (int64_t)X->rows, C, one_col);
+      lmf_one_col_kernel<<<grid, 256, 0, stream()>>>(x, (int64_t)X->rows, C, one_col);
       IMP_CHECK_HIP(hipGetLastError());
     }
     sync();  // synchronous, deferred mode included

@@ -87,8 +87,6 @@ void pair_update(const char *who, const char *check_prof, const char *prof, cons
   IMP_CHECK_HIP(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), stream()));
   check_pair_ids(who, check_prof, userids, itemids, indptr, X->rows, Y->rows, stats + 2);
 
-  note_device_write(X->data, X->bytes());  // cached top-k planes and padded copies made from X or Y are stale after this
-  note_device_write(Y->data, Y->bytes());
   {
     IMP_PROF(prof);
     const int G = pair_group_lanes((int)X->cols);

@@ -72,7 +72,7 @@ int imp_random_uniform(imp_random *r, size_t rows, size_t cols, float low, float
     if (n) {
       IMP_PROF("rng_uniform");
       int grid = (int)std::min<size_t>((n / 4 + 255) / 256 + 1, (size_t)ctx().num_cus * 8);
-      uniform_kernel<<<grid, 256, 0, stream()>>>(m->f32(), n, r->seed, r->draws++, low, high);
+      uniform_kernel<<<grid, 256, 0, stream()>>>(m->mut<float>(), n, r->seed, r->draws++, low, high);
       IMP_CHECK_HIP(hipGetLastError());
     }
     sync();
@@ -87,7 +87,7 @@ int imp_random_randn(imp_random *r, size_t rows, size_t cols, float mean, float 
     if (n) {
       IMP_PROF("rng_normal");
       int grid = (int)std::min<size_t>((n / 4 + 255) / 256 + 1, (size_t)ctx().num_cus * 8);
-      normal_kernel<<<grid, 256, 0, stream()>>>(m->f32(), n, r->seed, r->draws++, mean, stddev);
+      normal_kernel<<<grid, 256, 0, stream()>>>(m->mut<float>(), n, r->seed, r->draws++, mean, stddev);
       IMP_CHECK_HIP(hipGetLastError());
     }
     sync();

@@ -201,11 +201,11 @@ template <typename TI, typename TQ> static void rank_chunk(const RankCall &c, si
   if (c.n > 0) d_ids.alloc(out);
   if (c.n > 0 && c.any_long) d_scratch.alloc((size_t)nc);
   const size_t lds = rank_lds_bytes(c.lds_keys);
-  const TQ *q = reinterpret_cast<const TQ *>(c.query->data) + r0 * w;
+  const TQ *q = c.query->as<TQ>() + r0 * w;
   {
     IMP_PROF("rank");
     rank_kernel<TI, TQ><<<(unsigned int)rows, kRankBlock, lds, stream()>>>(
-        reinterpret_cast<const TI *>(c.items->data), (int)w, q, d_off.data(), d_cand.data(), c.liked_indptr ? d_lptr.data() : nullptr,
+        c.items->as<TI>(), (int)w, q, d_off.data(), d_cand.data(), c.liked_indptr ? d_lptr.data() : nullptr,
         d_lidx.data(), c.n, c.lds_keys, d_scratch.data(), d_ids.data(), d_scores.data());
     IMP_CHECK_HIP(hipGetLastError());
   }

@@ -156,8 +156,7 @@ extern "C" int imp_slim_solve(const imp_matrix *A, float l1, int positive, int m
     if (!A || !W) throw std::invalid_argument("slim_solve: NULL argument");
     if (A->itemsize != 4 || W->itemsize != 4 || A->rows != A->cols || W->rows != W->cols || A->rows != W->rows)
       throw std::invalid_argument("slim_solve: A and W must be square float32 matrices of the same order");
-    const char *a0 = static_cast<const char *>(A->data), *w0 = static_cast<const char *>(W->data);
-    if (A->bytes() && a0 < w0 + W->bytes() && w0 < a0 + A->bytes()) throw std::invalid_argument("slim_solve: A and W must not share storage");
+    if (A->overlaps(W)) throw std::invalid_argument("slim_solve: A and W must not share storage");
     if (!std::isfinite(l1) || l1 < 0.f) throw std::invalid_argument("slim_solve: l1 must be finite and >= 0");
     if (!std::isfinite(tol) || tol < 0.f) throw std::invalid_argument("slim_solve: tol must be finite and >= 0");
     if (max_sweeps < 1) throw std::invalid_argument("slim_solve: max_sweeps must be >= 1");
@@ -191,20 +190,20 @@ extern "C" int imp_slim_solve(const imp_matrix *A, float l1, int positive, int m
     IMP_CHECK_HIP(hipMemcpyAsync(order, h_order.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, stream()));
     sync();  // no copy from or to the two host vectors is queued past this line: a failure below may unwind them
     IMP_CHECK_HIP(hipMemsetAsync(words, 0, 6 * sizeof(int), stream()));
-    note_device_write(W->data, W->bytes());
+    float *const w = W->mut<float>();
     const size_t lds = slim_lds_bytes(n);
     allow_dynamic_lds(slim_cd_kernel, lds);
     {
       IMP_PROF("slim_cd");
       const unsigned grid = (unsigned)std::min(n, (size_t)2 * c.num_cus);
       slim_cd_kernel<<<grid, kSlimBlock, lds, stream()>>>(A->f32(), diag, order, (int)n, (int)((n + 3) / 4 * 4), l1, positive ? 1 : 0,
-                                                          max_sweeps, tol, W->f32(), d_sweeps, words, stats);
+                                                          max_sweeps, tol, w, d_sweeps, words, stats);
       IMP_CHECK_HIP(hipGetLastError());
     }
     {
       IMP_PROF("slim_transpose");
       const unsigned tiles = (unsigned)((n + kTile - 1) / kTile);
-      slim_transpose_kernel<<<dim3(tiles, tiles), 256, 0, stream()>>>(W->f32(), (int)n);
+      slim_transpose_kernel<<<dim3(tiles, tiles), 256, 0, stream()>>>(w, (int)n);
       IMP_CHECK_HIP(hipGetLastError());
     }
     if (sweeps) IMP_CHECK_HIP(hipMemcpyAsync(sweeps, d_sweeps, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));

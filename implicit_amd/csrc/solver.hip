@@ -84,16 +84,14 @@ static void launch_loss(const imp_csr *C, const float *X, const float *Y, const 
                                                                YtY, f, buf);
 }
 
-// rows of X <-> rows of one block of a (possibly multi-block) CSR matrix
-template <typename Fn> static void for_each_part(const imp_csr *C, const imp_matrix *X, Fn &&fn) {
+// rows of X <-> rows of one block of a (possibly multi-block) CSR matrix; Matrix is imp_matrix or const imp_matrix, and so is the view
+template <typename Matrix, typename Fn> static void for_each_part(const imp_csr *C, Matrix *X, Fn &&fn) {
   if (C->parts.empty()) {
     fn(C, X);
     return;
   }
   for (size_t i = 0; i < C->parts.size(); ++i) {
-    imp_matrix view = *X;  // row-range view sharing storage
-    view.rows = (size_t)C->parts[i]->rows;
-    view.data = reinterpret_cast<char *>(X->data) + (size_t)C->part_row0[i] * X->cols * X->itemsize;
+    Matrix view = X->rows_view((size_t)C->part_row0[i], (size_t)C->parts[i]->rows);
     fn(C->parts[i].get(), &view);
   }
 }
@@ -102,8 +100,8 @@ template <typename Fn> static void for_each_part(const imp_csr *C, const imp_mat
 template <typename Fn> static int64_t first_failed_row(const imp_csr *C, imp_matrix *X, Fn &&solve) {
   int64_t failed = -1;
   size_t block = 0;
-  for_each_part(C, X, [&](const imp_csr *part, const imp_matrix *xp) {
-    const int64_t bad = solve(part, const_cast<imp_matrix *>(xp));
+  for_each_part(C, X, [&](const imp_csr *part, imp_matrix *xp) {
+    const int64_t bad = solve(part, xp);
     if (bad >= 0 && failed < 0) failed = bad + (C->parts.empty() ? 0 : C->part_row0[block]);
     ++block;
   });
@@ -186,8 +184,8 @@ int imp_solver_calculate_yty(imp_solver *, const imp_matrix *Y, imp_matrix *YtY,
     if (YtY->cols != Y->cols) throw std::invalid_argument("YtY and Y should have the same number of columns");
     if (YtY->rows != YtY->cols) throw std::invalid_argument("YtY must be square");
     if (YtY->itemsize != 4) throw std::invalid_argument("YtY must be float32");
-    if (Y->itemsize == 4) gramian(Y->f32(), (long)Y->rows, (int)Y->cols, regularization, YtY->f32());
-    else gramian_half(Y->data, (long)Y->rows, (int)Y->cols, regularization, YtY->f32());  // converted in registers
+    if (Y->itemsize == 4) gramian(Y->f32(), (long)Y->rows, (int)Y->cols, regularization, YtY->mut<float>());
+    else gramian_half(Y->as(), (long)Y->rows, (int)Y->cols, regularization, YtY->mut<float>());  // converted in registers
     sync_call();
   });
 }
@@ -198,11 +196,12 @@ static void run_with_f32(const imp_csr *cui, imp_matrix *X, const imp_matrix *Y,
     body(X, Y);
     return;
   }
-  // fp16 storage: up-convert, solve in fp32, down-convert X back in place
+  // fp16 storage: up-convert, solve in fp32, down-convert the solved rows of X back in place (the others came through unchanged)
   const auto x32 = astype(X, 4), y32 = astype(Y, 4);
   body(x32.get(), y32.get());
   const auto x16 = astype(x32.get(), 2);
-  IMP_CHECK_HIP(hipMemcpyAsync(X->data, x16->data, X->bytes(), hipMemcpyDeviceToDevice, stream()));
+  const size_t solved = (size_t)cui->rows;
+  IMP_CHECK_HIP(hipMemcpyAsync(X->mut_rows(0, solved), x16->as(), solved * X->cols * X->itemsize, hipMemcpyDeviceToDevice, stream()));
   sync();
 }
 
@@ -211,13 +210,8 @@ int imp_solver_least_squares(imp_solver *, const imp_csr *cui, imp_matrix *X, co
   return guarded([&] {
     check_solver_args(cui, X, YtY, Y);
     if (cg_steps < 0) throw std::invalid_argument("cg_steps must be >= 0");
-    // the rows this call solves, in the CALLER's matrix: least_squares_cg reports the write on the matrix it is handed, which for
-    // fp16 factors outside the native factor counts is an fp32 temporary (run_with_f32 copies the result back)
-    note_device_write(X->data, (size_t)cui->rows * X->cols * X->itemsize);
     auto body = [&](imp_matrix *x, const imp_matrix *y) {
-      for_each_part(cui, x, [&](const imp_csr *part, const imp_matrix *xp) {
-        least_squares_cg(part, const_cast<imp_matrix *>(xp), YtY, y, cg_steps);
-      });
+      for_each_part(cui, x, [&](const imp_csr *part, imp_matrix *xp) { least_squares_cg(part, xp, YtY, y, cg_steps); });
       if (ctx().deferred) return;
       sync();
     };
@@ -232,7 +226,6 @@ int imp_solver_least_squares_cholesky(imp_solver *, const imp_csr *cui, imp_matr
                                       const imp_matrix *Y, double regularization, int64_t *failed_row) {
   return guarded([&] {
     check_solver_args(cui, X, YtY, Y);
-    note_device_write(X->data, X->bytes());  // the rows this call solves
     int64_t failed = -1;
     run_with_f32(cui, X, Y, [&](imp_matrix *x, const imp_matrix *y) {
       failed = first_failed_row(cui, x, [&](const imp_csr *part, imp_matrix *xp) {
@@ -255,7 +248,6 @@ int imp_solver_least_squares_subspace(imp_solver *, const imp_csr *cui, imp_matr
     if (X->cols > 1024) throw std::invalid_argument("least_squares_subspace: factors must be <= 1024");
     if (block_size < 1 || block_size > 32) throw std::invalid_argument("least_squares_subspace: block_size must be 1 .. 32");
     if (sweeps < 1) throw std::invalid_argument("least_squares_subspace: sweeps must be >= 1");
-    note_device_write(X->data, (size_t)cui->rows * X->cols * X->itemsize);  // the rows this call solves
     const int64_t failed = first_failed_row(cui, X, [&](const imp_csr *part, imp_matrix *xp) {
       return least_squares_subspace(part, xp, YtY, Y, regularization, block_size, sweeps);
     });

@@ -371,8 +371,7 @@ extern "C" int imp_spd_inverse(imp_matrix *A, int64_t *failed_pivot) {
     if (A->rows > (size_t)INT32_MAX - 256) throw std::invalid_argument("spd_inverse: the order must stay below 2^31 - 256");
     if (A->rows == 0) return;
     IMP_PROF("spd_inverse");
-    note_device_write(A->data, A->bytes());
-    const int64_t failed = spd_inverse(A->f32(), A->rows);
+    const int64_t failed = spd_inverse(A->mut<float>(), A->rows);
     if (failed >= 0) {
       if (failed_pivot) *failed_pivot = failed;
       throw std::invalid_argument("spd_inverse: the matrix is not positive definite (pivot " + std::to_string(failed) + " is not positive)");

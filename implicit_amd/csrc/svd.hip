@@ -272,11 +272,6 @@ __global__ __launch_bounds__(256) void multiply_small_kernel(const float *__rest
       }
     }
 }
-
-bool overlap(const imp_matrix *a, const imp_matrix *b) {
-  const char *pa = static_cast<const char *>(a->data), *pb = static_cast<const char *>(b->data);
-  return a->bytes() && b->bytes() && pa < pb + b->bytes() && pb < pa + a->bytes();
-}
 }  // namespace
 
 }  // namespace imp
@@ -292,10 +287,9 @@ extern "C" int imp_csr_spmm(const imp_csr *A, const imp_matrix *D, imp_matrix *o
       throw std::invalid_argument("csr_spmm: D must have 1 .. " + std::to_string(kSpmmMaxCols) + " columns");
     if (D->rows != (size_t)A->cols || out->rows != (size_t)A->rows || out->cols != D->cols)
       throw std::invalid_argument("csr_spmm: A (rows x cols), D (cols x l) and out (rows x l) do not agree");
-    if (overlap(out, D)) throw std::invalid_argument("csr_spmm: out must not share storage with D");
+    if (out->overlaps(D)) throw std::invalid_argument("csr_spmm: out must not share storage with D");
     if (A->rows == 0) return;
-    note_device_write(out->data, out->bytes());
-    spmm_launch(A, D->f32(), (int)D->cols, out->f32());
+    spmm_launch(A, D->f32(), (int)D->cols, out->mut<float>());
     sync_call();
   });
 }
@@ -309,14 +303,13 @@ extern "C" int imp_matrix_multiply_small(const imp_matrix *Y, const imp_matrix *
       throw std::invalid_argument("matrix_multiply_small: W must be l x m with l and m in 1 .. " + std::to_string(kSpmmMaxCols));
     if (Y->cols != W->rows || out->rows != Y->rows || out->cols != W->cols)
       throw std::invalid_argument("matrix_multiply_small: Y (rows x l), W (l x m) and out (rows x m) do not agree");
-    if (overlap(out, Y) || overlap(out, W)) throw std::invalid_argument("matrix_multiply_small: out must not share storage with Y or W");
+    if (out->overlaps(Y) || out->overlaps(W)) throw std::invalid_argument("matrix_multiply_small: out must not share storage with Y or W");
     if (Y->rows == 0) return;
     const size_t row_tiles = (Y->rows + kMulTile - 1) / kMulTile;
     IMP_PROF("multiply_small");
-    note_device_write(out->data, out->bytes());
     const int l = (int)W->rows, m = (int)W->cols;
     multiply_small_kernel<<<dim3((unsigned)row_tiles, (unsigned)((m + kMulTile - 1) / kMulTile)), 256, 0, stream()>>>(
-        Y->f32(), (long)Y->rows, l, W->f32(), m, out->f32());
+        Y->f32(), (long)Y->rows, l, W->f32(), m, out->mut<float>());
     IMP_CHECK_HIP(hipGetLastError());
     sync_call();
   });

@@ -655,7 +655,7 @@ struct imp_knn {
   DeviceArray<float> pad_items, pad_query;  // zero-padded fp32 copies for factor counts that are not a multiple of 16
   DeviceArray<split_bf16> query_split;      // [nq][3][f] bf16 (or [nq][2][f] fp16) terms of the query rows (emit path, split forms)
   // fp16 two-term form (topk_resident.h): the item matrix as fragment-ordered planes, made once per catalogue VERSION -- `key`
-  // names the memory they were made from and is cleared by any write to it through the library (note_device_write); memory the
+  // names the memory they were made from and is cleared by any write to it through the library (imp_matrix::mut_rows); memory the
   // library cannot vouch for (wrapped foreign pointers, matrices whose address was handed out) is split again on every call
   struct ItemPlanes {
     DerivedCache key;
@@ -797,10 +797,10 @@ struct TopkOperands {
 // factor counts that are not a multiple of 16 (the reference's CPU default is 100): rows zero-padded to the next multiple, fp16
 // converted on the way -- extra zero factors change no dot product, and the scores come from the direct-operand kernels
 template <typename T> static void pad_factors(const imp_matrix *m, float *out, int f) {
-  pad_rows(std::max(1, grid_1d(m->rows * (size_t)f, 16)), static_cast<const T *>(m->data), out, m->rows, (int)m->cols, f);
+  pad_rows(std::max(1, grid_1d(m->rows * (size_t)f, 16)), m->as<T>(), out, m->rows, (int)m->cols, f);
 }
 static TopkOperands prepare_operands(imp_knn *knn, const imp_matrix *items_in, const imp_matrix *query_in, int f, bool fast) {
-  TopkOperands op{items_in->data, query_in->data, items_in->itemsize == 2, nullptr, nullptr};
+  TopkOperands op{items_in->as(), query_in->as(), items_in->itemsize == 2, nullptr, nullptr};
   if (f != (int)items_in->cols) {
     float *pi = knn->pad_items.reserve(items_in->rows * (size_t)f), *pq = knn->pad_query.reserve(query_in->rows * (size_t)f);
     IMP_PROF("pad_factors");
@@ -811,7 +811,7 @@ static TopkOperands prepare_operands(imp_knn *knn, const imp_matrix *items_in, c
   } else if (op.half && !fast) {
     op.items_conv = astype(items_in, 4);
     op.query_conv = astype(query_in, 4);
-    op.items = op.items_conv->data, op.query = op.query_conv->data, op.half = false;
+    op.items = op.items_conv->as(), op.query = op.query_conv->as(), op.half = false;
   }
   return op;
 }
@@ -824,12 +824,11 @@ template <typename TQ, typename TI> static ResidentArgs split_planes(const TopkC
   const size_t nq = c.nq, ni = c.ni, ni_pad = (ni + 127) / 128 * 128, F = (size_t)KS * 16;
   const int f = c.f;
   auto &ip = c.knn->item_planes;
-  // memory the library cannot vouch for never hits, whatever the key says (the address may have been handed out after the planes were made)
-  const bool trusted = items_in->storage && items_in->storage->owned && !items_in->storage->exposed;
-  const bool same = trusted && ip.key.src == items_in->data && ip.rows == ni && ip.cols == items_in->cols && ip.itemsize == items_in->itemsize && ip.KS == KS;
+  // (memory the library cannot vouch for never hits: the address may have been handed out after the planes were made)
+  const bool same = ip.key.made_from(items_in) && ip.rows == ni && ip.cols == items_in->cols && ip.itemsize == items_in->itemsize && ip.KS == KS;
   if (!same) {
     IMP_PROF_NESTED("item_planes_split");  // one count per (re)build of the item planes: what the cache tests read
-    ip.key.src = nullptr;
+    ip.key.drop();
     ip.planes.reserve(ni_pad * F * 2), ip.exp.reserve(1), ip.maxbits.reserve(1), ip.ne.reserve(4), ip.tile_n.reserve(ni_pad / 32);
     IMP_CHECK_HIP(hipMemsetAsync(ip.maxbits.data(), 0, sizeof(unsigned), stream()));
     IMP_CHECK_HIP(hipMemsetAsync(ip.ne.data(), 0, 4 * sizeof(unsigned), stream()));
@@ -840,7 +839,7 @@ template <typename TQ, typename TI> static ResidentArgs split_planes(const TopkC
     rq_item_err_kernel<TI><<<(int)std::min<size_t>((ni + 3) / 4, (size_t)ctx().num_cus * 16), 256, 0, stream()>>>(Ib, ni, f, ip.exp.data(),
                                                                                                               ip.ne.data(), ip.tile_n.data());
     ip.rows = ni, ip.cols = items_in->cols, ip.itemsize = items_in->itemsize, ip.KS = KS;
-    if (trusted) ip.key.src = items_in->data, ip.key.bytes = items_in->bytes();
+    ip.key.bind(items_in);
   }
   const size_t nq_pad = rq_query_pad(nq);
   _Float16 *qp = c.knn->query_planes.reserve(nq_pad * F * 2);

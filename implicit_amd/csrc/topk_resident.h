@@ -8,7 +8,7 @@
 //   * K = f is small (<= 256) and the catalogue is long: a wavefront keeps its query rows' A fragments for ALL of K in
 //     registers (2 tiles x 8 k-steps x 2 terms x 4 VGPRs = 128 at f = 128) and only the ITEM operand streams;
 //   * the item matrix is split ONCE per catalogue version into fragment-ordered fp16 planes (item_split_kernel; cached in the
-//     KnnQuery handle, invalidated through note_device_write): a 32-item tile is KS x 2 KB of contiguous memory, moved by LDS-DMA
+//     KnnQuery handle, invalidated by the write accessors of imp_matrix): a 32-item tile is KS x 2 KB of contiguous memory, moved by LDS-DMA
 //     as it lies and read back by lane-linear ds_read_b128 -- no split, no swizzle, no conversion in the loop;
 //   * persistent workgroups (2 per CU, 4 wavefronts, 128 TQ queries) walk a contiguous range of item tiles through a ring of
 //     LDS slots: ONE raw s_barrier per tile (48 MFMAs per wavefront at f = 128), the DMA of the next NSTAGE - 1 tiles in flight

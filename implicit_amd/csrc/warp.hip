@@ -159,7 +159,7 @@ extern "C" int imp_warp_update(const imp_intvector *userids, const imp_intvector
     if (Y && Y->rows > (size_t)INT32_MAX) throw std::invalid_argument("warp_update: more than 2^31 - 1 items");
     pair_update("warp_update", "warp_check_ids", "warp_update", userids, itemids, indptr, X, Y, samples, satisfied, trials,
                 [&](int G, int grid, int64_t n, unsigned long long *stats) {
-                  const WarpArgs a{userids->v.data(), itemids->v.data(), indptr->v.data(), X->f32(), Y->f32(), (int64_t)userids->size, n,
+                  const WarpArgs a{userids->v.data(), itemids->v.data(), indptr->v.data(), X->mut<float>(), Y->mut<float>(), (int64_t)userids->size, n,
                                    (uint64_t)seed, learning_rate, regularization, (int)X->cols, (int)Y->rows, max_sampled, stats};
                   for_group_shape<false>(G, a.C, [&](auto g, auto cpl) {
                     warp_update_kernel<decltype(g)::value, decltype(cpl)::value><<<grid, 256, 0, stream()>>>(a);

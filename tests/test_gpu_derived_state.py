@@ -2,9 +2,10 @@
 
 Derived state (csrc/common.h): the fragment-ordered fp16 item planes of a KnnQuery handle (topk.hip, split_planes), the
 zero-padded copy of Y of the padded CG half sweep (als_pad.hip, pad_in), and on the Python side the top-k handle, norms and
-gramians a model keeps.  Each is right only while every path that rewrites the matrix says so (note_device_write), or while the
-library refuses to keep anything of memory it cannot watch.  A miss gives no crash and no NaN: it gives the previous
-contents' answer.
+gramians a model keeps.  Each is right only while every write to the matrix is reported, or while the library refuses to keep
+anything of memory it cannot watch.  Inside the library that is no longer a line per writer: the only way to a mutable device
+pointer of a matrix is its write accessor (imp_matrix::mut_rows, common.h), which reports exactly the bytes it hands out.  A
+miss gives no crash and no NaN: it gives the previous contents' answer.
 
 A cell = one writer x one consumer, always the same four beats:
   1. the matrix holds A; the consumer's answer is the reference's for A;
@@ -26,7 +27,8 @@ test_padded_copy_of_y_is_reused_only_while_it_is_valid does, so that only the wr
 Writers: 1 copy_from_numpy, 2 assign_rows (every third row), 3 copy_rows_from (a row range), 4 resize + copy_from_numpy and
 destroy + create (the pool hands the freed block out again), 5 CG sweep and 6 Cholesky sweep into the matrix (all rows, and a
 row-slice view), 8 a write through an address obtained with device_ptr AFTER the cache was live, 9 foreign memory wrapped
-through __cuda_array_interface__ and rewritten behind the library's back.
+through __cuda_array_interface__ and rewritten behind the library's back, 10 calculate_yty with the matrix as its OUTPUT (a
+square Y, 100 items x 100 factors: the one writer that had no notification line of its own).
 
 Cells left out, and why:
   * 7 bpr_epoch / lmf_update x planes: test_gpu_bpr.py::test_plane_cache_invalidated_by_bpr_epoch and
@@ -357,11 +359,13 @@ def test_planes_follow_solver_sweeps(gpu, oracle, solver_kind, f, dtype, rows):
 
 # ---- consumer 2: the zero-padded copy of Y of the padded CG half sweep --------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def pad_inputs(f):
-    C = synthetic_csr(600, 300, 9000, seed=11, empty_frac=0.03)
+def pad_inputs(f, square=False):
+    """square: Y has as many rows (items) as columns, so that it can stand where a gramian is written."""
+    users, items = (48, f) if square else (600, 300)
+    C = synthetic_csr(users, items, 15 * users, seed=11, empty_frac=0.1 if square else 0.03)
     assert (np.diff(C.indptr) == 0).any()
     rng = np.random.default_rng(f)
-    X0, YA, YB, big = (rng.random((n, f), dtype=np.float32) * 0.2 - 0.1 for n in (600, 300, 300, 300))
+    X0, YA, YB, big = (rng.random((n, f), dtype=np.float32) * 0.2 - 0.1 for n in (users, items, items, items))
     big = big * np.float32(PARTIAL_SCALE)
     for m in (X0, YA, YB, big):
         m.setflags(write=False)
@@ -379,6 +383,15 @@ def w_cholesky_sweep_into_y(cell, a, b, big):
     return cell.m.to_numpy()
 
 
+def w_gramian_into_y(cell, a, b, big):
+    """Writer 10: the matrix that is Y here is the output of calculate_yty (Z^T Z of a small random Z of as many columns)."""
+    gpu, f = cell.gpu, a.shape[1]
+    assert a.shape == (f, f)
+    Z = (np.random.default_rng(f + 1).random((16, f), dtype=np.float32) * 0.4 - 0.2).astype(np.float32)
+    gpu.LeastSquaresSolver().calculate_yty(gpu.Matrix(Z), cell.m, 0.0)
+    return cell.m.to_numpy()
+
+
 def rows_rel(got, want, lens):
     """Worst relative distance of a non-empty row; empty rows must be zero."""
     assert not got[lens == 0].any()
@@ -386,12 +399,13 @@ def rows_rel(got, want, lens):
     return float((diff / np.maximum(np.linalg.norm(want.astype(np.float64), axis=1)[lens > 0], 1e-30)).max())
 
 
-PAD_CELLS = ([(f, w) for f in (100, 32) for w in CONTAINER_WRITERS + UNTRACKED_WRITERS] + [(32, w_cholesky_sweep_into_y)])
+PAD_CELLS = ([(f, w) for f in (100, 32) for w in CONTAINER_WRITERS + UNTRACKED_WRITERS] + [(32, w_cholesky_sweep_into_y)]
+             + [(100, w_gramian_into_y)])
 
 
 @pytest.mark.parametrize("f,writer", PAD_CELLS, ids=lambda v: writer_id(v) if callable(v) else str(v))
 def test_padded_copy_of_y_follows_writes(gpu, oracle, f, writer):
-    C, X0, YA, YB, big = pad_inputs(f)
+    C, X0, YA, YB, big = pad_inputs(f, square=writer is w_gramian_into_y)
     lens = np.diff(C.indptr)
     foreign = writer is w_foreign_rewrite
     trusted = not foreign
