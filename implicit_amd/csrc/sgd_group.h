@@ -83,6 +83,15 @@ __device__ __forceinline__ bool group_row_contains(const int32_t *__restrict__ i
   return (__builtin_amdgcn_ballot_w64(p < hi && itemids[p] == j) & gmask) != 0;
 }
 
+// A store of a WARP update (warp.hip, hybrid_warp.hip): agent scope (global_store ... sc1), which writes through the XCD's L2
+// and does not keep the line there.  A plain store stays dirty in the writing XCD's L2 until the kernel ends and stays valid
+// there afterwards; where workgroups on two XCDs wrote or read the same line during the call, a LATER kernel scheduled on one
+// of them then read that XCD's version while memory -- and every copy to the host -- held the other's: measured, about 900 of
+// 16 000 item rows after an epoch, until other traffic evicted the lines.  With these stores no row differed.
+__device__ __forceinline__ void store_through(float *p, float v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Two per-lane counts of a 256-thread workgroup into stats[0] and stats[1]: wave sum, then one atomic per workgroup.  Every
 // thread of the workgroup calls it.
 __device__ __forceinline__ void block_add_counts(unsigned long long c0, unsigned long long c1, unsigned long long *stats) {

@@ -45,15 +45,6 @@
 
 namespace imp {
 
-// A store of the update: agent scope (global_store ... sc1), which writes through the XCD's L2 and does not keep the line
-// there.  A plain store stays dirty in the writing XCD's L2 until the kernel ends and stays valid there afterwards; where
-// workgroups on two XCDs wrote or read the same line during the call, a LATER kernel scheduled on one of them then read
-// that XCD's version while memory -- and every copy to the host -- held the other's: measured, about 900 of 16 000 item
-// rows after an epoch, until other traffic evicted the lines.  With these stores no row differed.
-__device__ __forceinline__ void store_through(float *p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 struct WarpArgs {
   const int32_t *__restrict__ userids;
   const int32_t *__restrict__ itemids;

@@ -487,6 +487,28 @@ def warp_epoch(userids, itemids, indptr, X, Y, learning_rate, regularization, se
     return satisfied.value, trials.value
 
 
+def hybrid_warp_epoch(userids, itemids, indptr, user_features, item_features, EU, EI, learning_rate, regularization, seed,
+                      max_sampled=10, samples=None):
+    """NEW: one SGD pass of WARP-loss factorization over user and item features (imp_hybrid_warp_update, hybrid_warp.hip),
+    returns (satisfied, trials).  userids / itemids / indptr, max_sampled and samples: as warp_epoch.  user_features (users x
+    UF) and item_features (items x IF): CSRMatrix objects; EU (UF x C) and EI (IF x C): float32 embedding Matrix objects,
+    updated in place.  A user or item is the weighted sum of its features' embeddings; column C - 1 is the bias (1.0 for
+    every user, EU's last column is never touched).  Bad arguments raise ValueError, an id outside its matrix IndexError
+    before anything is written."""
+    for name, v in (("userids", userids), ("itemids", itemids), ("indptr", indptr)):
+        if not isinstance(v, IntVector):
+            raise TypeError(f"hybrid_warp_epoch: {name} must be an implicit_amd.gpu.IntVector")
+    if not isinstance(user_features, CSRMatrix) or not isinstance(item_features, CSRMatrix):
+        raise TypeError("hybrid_warp_epoch: user_features and item_features must be implicit_amd.gpu.CSRMatrix objects")
+    if not isinstance(EU, Matrix) or not isinstance(EI, Matrix):
+        raise TypeError("hybrid_warp_epoch: EU and EI must be implicit_amd.gpu.Matrix objects")
+    satisfied, trials = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().imp_hybrid_warp_update(userids._h, itemids._h, indptr._h, user_features._h, item_features._h, EU._h, EI._h,
+                                       float(learning_rate), float(regularization), int(seed), int(max_sampled),
+                                       -1 if samples is None else int(samples), ctypes.byref(satisfied), ctypes.byref(trials)))
+    return satisfied.value, trials.value
+
+
 def lmf_update(cui, X, Y, deriv_sum_sq, learning_rate, regularization, neg_prop, seed, one_col=-1):
     """One Adagrad half-sweep of Logistic Matrix Factorization (imp_lmf_update, lmf.hip): X is updated in place against
     the read-only Y over the CSRMatrix `cui` (rows of X x rows of Y, values = confidences), deriv_sum_sq (the shape of X)

@@ -304,6 +304,26 @@ int imp_warp_update(const imp_intvector *userids, const imp_intvector *itemids, 
                     imp_matrix *Y, float learning_rate, float regularization, int64_t seed, int max_sampled, int64_t samples,
                     int64_t *satisfied, int64_t *trials);
 
+/* ---- NEW: one SGD pass of WARP-loss factorization over user and item features (Kula 2015, the model of LightFM, under the
+ * loss above; no reference counterpart; csrc/hybrid_warp.hip states the contract in full).  userids, itemids, indptr:
+ * the interaction pattern as imp_warp_update takes it.  user_features (users x UF) and item_features (items x IF): CSR
+ * matrices with fp32 values and no repeated column within a row; EU (UF x C) and EI (IF x C): fp32 embeddings, C = factors + 1
+ * in 2 .. 1024.  A user is x = sum of w EU[a] over its feature row (an fp32 fmaf chain in stored order, x[C-1] = 1.0 by
+ * definition: column C-1 of EU is never read or written), an item y = the same over EI, column C-1 the item bias; an empty
+ * feature row gives zeros.  Positives, candidates, the violation test and the weight are imp_warp_update's, drawn from Philox
+ * streams tagged 5; the step scatters E[a] += lr (w g - reg E[a]) over the feature rows of the user, the positive and then
+ * the negative, which re-reads the rows it updates: a feature both items share receives both steps in that order.  A
+ * satisfied sample writes nothing.  *satisfied, *trials: as imp_warp_update.  Synchronous, deferred mode included.
+ * IMP_OUT_OF_RANGE (IndexError) from the device pre-pass, EU and EI untouched: a user id outside [0, user_features.rows), an
+ * item id outside [0, item_features.rows), an indptr entry outside [0, nnz], a feature column id outside its embedding matrix.
+ * IMP_INVALID_ARGUMENT: column counts differ or outside 2 .. 1024, a matrix not fp32, EU and EI sharing storage, max_sampled
+ * outside 1 .. 4096, userids / itemids of different sizes, indptr not user_features.rows + 1 long, EU.rows != UF or EI.rows !=
+ * IF, a feature matrix of more than 2^31 - 1 nonzeros.  nnz = 0 returns (0, 0) without a launch. */
+int imp_hybrid_warp_update(const imp_intvector *userids, const imp_intvector *itemids, const imp_intvector *indptr,
+                           const imp_csr *user_features, const imp_csr *item_features, imp_matrix *EU, imp_matrix *EI,
+                           float learning_rate, float regularization, int64_t seed, int max_sampled, int64_t samples,
+                           int64_t *satisfied, int64_t *trials);
+
 /* ---- LMF training (no reference GPU counterpart: implicit/lmf.py raises for use_gpu=True) --------------------------- */
 /* One Adagrad half-sweep of Logistic Matrix Factorization: X (rows of cui x C) is updated against the read-only Y (columns
  * of cui x C), deriv_sum_sq (shape of X) accumulates the squared gradients.  fp32, C = factors + 2 in 3 .. 1024.  The
