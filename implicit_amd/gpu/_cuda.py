@@ -509,6 +509,29 @@ def hybrid_warp_epoch(userids, itemids, indptr, user_features, item_features, EU
     return satisfied.value, trials.value
 
 
+def softmax_epoch(userids, itemids, indptr, X, Y, learning_rate, regularization, seed, negatives=128, samples=None):
+    """NEW: one SGD pass of sampled-softmax matrix factorization (imp_softmax_update, softmax_mf.hip), returns (correct,
+    masked).  The arrays and matrices are those of bpr_epoch (row indices sorted); `samples`: the number of sampled positives,
+    None for one epoch (nnz).  The samples are taken in mini-batches of 64; each batch draws `negatives` items uniformly (a
+    multiple of 32 in 32 .. 256), shared by its rows, and every row takes a softmax step over its positive and the negatives
+    its user has not liked.  `correct` counts the rows whose positive outscored every such negative, `masked` the (row,
+    negative) pairs left out.  X / Y are updated in place.  Positives and negatives are Philox streams of (seed, sample or
+    batch index).  Bad arguments raise ValueError, an id outside its matrix IndexError before anything is written."""
+    for name, v in (("userids", userids), ("itemids", itemids), ("indptr", indptr)):
+        if not isinstance(v, IntVector):
+            raise TypeError(f"softmax_epoch: {name} must be an implicit_amd.gpu.IntVector")
+    if not isinstance(X, Matrix) or not isinstance(Y, Matrix):
+        raise TypeError("softmax_epoch: X and Y must be implicit_amd.gpu.Matrix objects")
+    negatives = int(negatives)
+    if not 32 <= negatives <= 256 or negatives % 32:
+        raise ValueError("softmax_epoch: negatives must be a multiple of 32 in 32 .. 256")
+    correct, masked = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().imp_softmax_update(userids._h, itemids._h, indptr._h, X._h, Y._h, float(learning_rate), float(regularization),
+                                   int(seed), negatives, -1 if samples is None else int(samples),
+                                   ctypes.byref(correct), ctypes.byref(masked)))
+    return correct.value, masked.value
+
+
 def lmf_update(cui, X, Y, deriv_sum_sq, learning_rate, regularization, neg_prop, seed, one_col=-1):
     """One Adagrad half-sweep of Logistic Matrix Factorization (imp_lmf_update, lmf.hip): X is updated in place against
     the read-only Y over the CSRMatrix `cui` (rows of X x rows of Y, values = confidences), deriv_sum_sq (the shape of X)

@@ -324,6 +324,30 @@ int imp_hybrid_warp_update(const imp_intvector *userids, const imp_intvector *it
                            float learning_rate, float regularization, int64_t seed, int max_sampled, int64_t samples,
                            int64_t *satisfied, int64_t *trials);
 
+/* ---- NEW: one SGD pass of sampled-softmax matrix factorization with shared negatives (Wu et al. 2022; no reference
+ * counterpart; csrc/softmax_mf.hip states the contract in full) over `samples` sampled positives (samples < 0: nnz,
+ * one epoch).  userids, itemids, indptr, X, Y: as imp_warp_update (fp32, C = factors + 1 in 2 .. 1024, column C-1 the item
+ * bias, 1.0 in every user row and never written in X; row indices sorted).  negatives = N: a multiple of 32 in 32 .. 256.
+ * Batch b holds the samples s = 64 b + r, r = 0 .. 63, s < samples; a partial last batch's missing rows contribute nothing.
+ * Sample s: Philox4x32-10(counter (s_lo, s_hi, 0, 6), key = seed) gives lp = (word 0 * nnz) >> 32 and (u_r, i_r) =
+ * (userids[lp], itemids[lp]).  The batch's N negatives are shared by its rows: slot n takes word n & 3 of Philox(counter
+ * (b_lo, b_hi, 1 + (n >> 2), 6)), j_n = (word * items) >> 32.  M[r][n] = 1 when j_n is in row u_r of the pattern (j_n = i_r
+ * included); a masked logit takes no part in row r's softmax.  From the values before the batch's update: z_r = X[u_r].Y[i_r],
+ * z_rn = X[u_r].Y[j_n], m_r their maximum over the unmasked, p_r and p_rn = exp(. - m_r) over their sum (p_rn = 0 where
+ * masked; all masked: p_r = 1).  For c < C-1: dX[u_r,c] = lr ((1 - p_r) Y[i_r,c] - sum_n p_rn Y[j_n,c] - reg X[u_r,c]),
+ * dY[i_r,c] = lr ((1 - p_r) X[u_r,c] - reg Y[i_r,c]), and once per slot n dY[j_n,c] = lr (-sum_r p_rn X[u_r,c] - reg Y[j_n,c]);
+ * bias: dY[i_r,C-1] = lr ((1 - p_r) - reg Y[i_r,C-1]), dY[j_n,C-1] = lr (-sum_r p_rn - reg Y[j_n,C-1]).  Every delta is ADDED
+ * to its row, so a user, positive or negative that occurs several times in a batch receives the sum of its occurrences'
+ * deltas.  *correct: rows with z_r > every unmasked z_rn; *masked: sum M.  max(1, (samples in flight of the BPR / WARP cap)
+ * / 64) batches are in flight; with min(users, items) < 2048 that is one, and the call is the serial mini-batch SGD above up
+ * to fp32 rounding.  Synchronous, deferred mode included.  Ids are checked on the device first: IMP_OUT_OF_RANGE (IndexError),
+ * X and Y untouched, as imp_bpr_update.  IMP_INVALID_ARGUMENT, X and Y untouched: negatives not a multiple of 32 in 32 .. 256,
+ * column counts differ or outside 2 .. 1024, a matrix not fp32, userids / itemids of different sizes, indptr not X.rows + 1
+ * long.  nnz = 0 returns (0, 0) without a launch. */
+int imp_softmax_update(const imp_intvector *userids, const imp_intvector *itemids, const imp_intvector *indptr, imp_matrix *X,
+                       imp_matrix *Y, float learning_rate, float regularization, int64_t seed, int negatives, int64_t samples,
+                       int64_t *correct, int64_t *masked);
+
 /* ---- LMF training (no reference GPU counterpart: implicit/lmf.py raises for use_gpu=True) --------------------------- */
 /* One Adagrad half-sweep of Logistic Matrix Factorization: X (rows of cui x C) is updated against the read-only Y (columns
  * of cui x C), deriv_sum_sq (shape of X) accumulates the squared gradients.  fp32, C = factors + 2 in 3 .. 1024.  The
