@@ -170,6 +170,13 @@ class IVFModel(RecommenderBase):
         return self.model.rank_items(userid, user_items, selected_items, N=N,
                                      filter_already_liked_items=filter_already_liked_items, recalculate_user=recalculate_user)
 
+    def diversify_items(self, userid, user_items, selected_items, N, rule="dpp", relevance_weight=0.7,
+                        filter_already_liked_items=False, recalculate_user=False):
+        """Exact: re-ranking given candidates does not search the index; forwarded to the wrapped model."""
+        return self.model.diversify_items(userid, user_items, selected_items, N, rule=rule, relevance_weight=relevance_weight,
+                                          filter_already_liked_items=filter_already_liked_items,
+                                          recalculate_user=recalculate_user)
+
     def score_items(self, userid, selected_items, user_items=None, recalculate_user=False):
         return self.model.score_items(userid, selected_items, user_items=user_items, recalculate_user=recalculate_user)
 

@@ -248,6 +248,7 @@ struct Context {
   DeviceArray<float> slim_diag;                  // the diagonal of A, copied aside by the check of imp_slim_solve (slim.hip)
   DeviceArray<int32_t> slim_ws;                  // its column order, sweep counts, ticket and the two counts of imp_slim_stats
   size_t slim_items = 0;                         // order of the last imp_slim_solve: where the counts sit in slim_ws
+  DeviceArray<float> div_basis;                  // Gram-Schmidt bases of a chunk of lists where they outgrow the LDS (diversify.hip)
 };
 inline hipStream_t stream() { return ctx().stream; }
 

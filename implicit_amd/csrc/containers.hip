@@ -498,6 +498,7 @@ int imp_release_workspaces(void) {
     c.slim_diag = {};
     c.slim_ws = {};
     c.slim_items = 0;
+    c.div_basis = {};
     std::lock_guard<std::mutex> g(c.small_mutex);
     for (auto &list : c.small_free) {
       for (void *p : list) (void)hipFree(p);

@@ -121,6 +121,33 @@ class KnnQuery:
                                  _vp(ids) if n > 0 else None, _vp(scores)))
         return (ids, scores) if n > 0 else scores
 
+    def diversify(self, items, offsets, candidates, quality, n, rule="dpp", param=0.5, min_gain=1e-6):
+        """NEW: a diversified re-rank of every candidate list -- list r is items[candidates[offsets[r]:offsets[r + 1]]], at most
+        4096 long, `quality` aligned with `candidates` -- by greedy DPP MAP inference (rule="dpp": kernel q_i q_j cos(y_i, y_j),
+        quality >= 0, `min_gain` the relative stop) or maximal marginal relevance (rule="mmr": `param` is lambda)
+        (csrc/diversify.hip; include/implicit_hip.h states both step by step).  Returns (ids, gains, counts): ids / gains
+        rows x n in pick order, padded with (-1, -FLT_MAX), counts the picks made per list."""
+        if not isinstance(items, Matrix):
+            raise TypeError("KnnQuery.diversify expects an implicit.gpu.Matrix of item factors")
+        if rule not in ("dpp", "mmr"):
+            raise ValueError("diversify: rule must be 'dpp' or 'mmr'")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        candidates = np.ascontiguousarray(candidates, dtype=np.int32)
+        quality = np.ascontiguousarray(quality, dtype=np.float32)
+        rows = len(offsets) - 1
+        if offsets.ndim != 1 or rows < 0 or candidates.ndim != 1 or len(candidates) != (offsets[-1] if rows else 0) or \
+                quality.shape != candidates.shape:
+            raise ValueError("diversify: offsets must hold one entry per list plus one and end at len(candidates) == len(quality)")
+        n = int(n)
+        if not 1 <= n < 2**31:
+            raise ValueError("diversify: n must be >= 1")
+        ids = np.zeros((rows, n), dtype=np.int32)
+        gains = np.zeros((rows, n), dtype=np.float32)
+        counts = np.zeros(rows, dtype=np.int32)
+        check(lib().imp_knn_diversify(self._h, items._h, rows, _vp(offsets), _vp(candidates), _vp(quality), n,
+                                      0 if rule == "dpp" else 1, float(param), float(min_gain), _vp(ids), _vp(gains), _vp(counts)))
+        return ids, gains, counts
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().imp_knn_destroy(self._h)

@@ -137,6 +137,37 @@ class MatrixFactorizationBase(RecommenderBase):
             return out
         return scores if np.isscalar(userid) else scores.reshape(len(offsets) - 1, len(selected_items))
 
+    def diversify_items(self, userid, user_items, selected_items, N, rule="dpp", relevance_weight=0.7,
+                        filter_already_liked_items=False, recalculate_user=False):
+        """NEW: a diversified re-rank of every user's own candidate list (KnnQuery.diversify; selected_items as in rank_items).
+        Relevance is score_items' score, similarity the cosine of the stored item factors.  rule="dpp": greedy MAP inference of
+        the DPP with kernel q_i q_j cos(i, j), q = exp(alpha (score - the list's best score)), alpha = relevance_weight /
+        (2 (1 - relevance_weight)) (Chen et al. 2018), relevance_weight in [0, 1); it stops early once a pick would add next to
+        nothing.  rule="mmr": maximal marginal relevance with lambda = relevance_weight in [0, 1].  Returns (ids, gains) in pick
+        order, [N] for a scalar userid and [B, N] otherwise, padded with (-1, -FLT_MAX).  A liked candidate is never picked
+        under DPP and comes last under MMR (filter_already_liked_items)."""
+        if rule not in ("dpp", "mmr"):
+            raise ValueError("rule must be 'dpp' or 'mmr'")
+        if int(N) < 1:
+            raise ValueError("N must be >= 1")
+        weight = float(relevance_weight)
+        if not (0 <= weight < 1 if rule == "dpp" else 0 <= weight <= 1):
+            raise ValueError("relevance_weight must lie in [0, 1) for rule='dpp' and in [0, 1] for rule='mmr'")
+        offsets, quality = self._rank(userid, user_items, selected_items, 0, filter_already_liked_items, recalculate_user)
+        candidates = candidate_lists(selected_items, len(offsets) - 1)[1]
+        if rule == "dpp":
+            liked = quality == -np.finfo(np.float32).max
+            score = np.where(liked, -np.inf, quality.astype(np.float64))
+            starts = offsets[:-1][np.diff(offsets) > 0]
+            best = np.full(len(offsets) - 1, -np.inf)
+            if len(starts):
+                best[np.diff(offsets) > 0] = np.maximum.reduceat(score, starts)
+            with np.errstate(invalid="ignore"):
+                quality = np.exp(weight / (2 * (1 - weight)) * (score - np.repeat(best, np.diff(offsets))))
+            quality = np.where(liked | np.isnan(quality), 0.0, quality).astype(np.float32)
+        ids, gains, _ = self.knn.diversify(self.item_factors, offsets, candidates, quality, int(N), rule, weight)
+        return (ids[0], gains[0]) if np.isscalar(userid) else (ids, gains)
+
     # ---- cosine similarity -------------------------------------------------------------------------
     def _similar(self, factors, norms_dev, norms_host, queryid, N, subset, filter_ids, what, query_factors=None):
         candidates, cand_norms = factors, norms_dev

@@ -268,6 +268,30 @@ int imp_knn_topk(imp_knn *k, const imp_matrix *items, const imp_matrix *query, i
 int imp_knn_rank(imp_knn *k, const imp_matrix *items, const imp_matrix *query, const int64_t *offsets,
                  const int32_t *candidates, int n, const int64_t *liked_indptr, const int32_t *liked_indices,
                  int32_t *indices, float *scores);
+/* NEW: a diversified re-rank of `rows` candidate lists (csrc/diversify.hip).  items (n_items x w): fp32 or fp16 (widened exactly),
+ * w in 1 .. 1024.  HOST inputs: offsets[rows + 1], candidates[offsets[rows]] and quality[offsets[rows]] (aligned with candidates);
+ * list r is candidates[offsets[r] .. offsets[r + 1]), at most 4096 long.  With y^_i the stored row of candidate i divided by its
+ * norm (an all-zero row stays zero), all arithmetic fp32:
+ *   rule 0, greedy MAP of the DPP with kernel L[i, j] = q_i q_j <y^_i, y^_j>, as column-pivoted Gram-Schmidt on b_i = q_i y^_i:
+ *     d2_i = |b_i|^2; basis U = {}; repeat up to n times:
+ *       j = argmax of d2 over the unpicked candidates (ties: larger id, then later position);
+ *       r = b_j, then twice: r -= sum_l <r, u_l> u_l;  g = |r|^2;
+ *       stop if g <= min_gain q_j^2, or once w picks are made (rank B <= w);
+ *       u = r / sqrt(g) joins U, j is picked with gain g;  d2_i -= <b_i, u>^2 for every i.
+ *     sum_k log gains[k] is the log-determinant of the picked sub-kernel.  min_gain in [0, 1) is the relative stop (the model
+ *     layer passes 1e-6).  A candidate of quality 0 or with a zero row is never picked; a repeated id is picked once.
+ *   rule 1, maximal marginal relevance: the value of i is param q_i - (1 - param) max over the picks j of <y^_i, y^_j> (the
+ *     maximum is 0 before the first pick); the largest value (ties as above) is picked with that value as its gain, until n
+ *     picks are made or the list is used up.  param in [0, 1]; min_gain is ignored.
+ * HOST outputs: indices / gains[rows x n] in pick order, the tail (-1, -FLT_MAX); counts[rows], the picks made.  Rows are processed
+ * in chunks that fit the handle's max_temp_memory; equal lists give equal bytes whatever the batch, the chunking, the launch shape
+ * or the calls before.  Deterministic: no atomics.  IMP_INVALID_ARGUMENT before any launch, nothing written: offsets that do not
+ * start at 0 or that decrease, an id outside [0, n_items), n < 1, a quality that is not finite (or negative under rule 0), a list
+ * of more than 4096 candidates, w outside 1 .. 1024, a matrix neither fp32 nor fp16, rule, param or min_gain out of range, rows
+ * outside 0 .. 2^31 - 1, a single row whose temporaries exceed max_temp_memory. */
+int imp_knn_diversify(imp_knn *k, const imp_matrix *items, int64_t rows, const int64_t *offsets, const int32_t *candidates,
+                      const float *quality, int n, int rule, float param, float min_gain, int32_t *indices, float *gains,
+                      int32_t *counts);
 
 /* ---- RandomState (random.h:10-21, random.cu:14-40) ------------------------------------------- */
 int imp_random_create(int64_t seed, imp_random **out);
