@@ -161,3 +161,115 @@ def AUC_at_k(model, train_user_items, test_user_items, K=10, show_progress=True,
              batch_size=DEFAULT_BATCH_SIZE):
     """Limited AUC at K of a fitted model (evaluation.pyx:334-362)."""
     return ranking_metrics_at_k(model, train_user_items, test_user_items, K, show_progress, num_threads, batch_size)["auc"]
+
+
+# ---- full-catalogue metrics (NEW: no counterpart in the reference) -----------------------------------------------------------
+def _full_rank_sums(ranks, offsets, candidates, Ks):
+    """The metrics of full_ranking_metrics from the ranks of KnnQuery.target_ranks (float64, host): `ranks` aligned with the
+    targets (-1: excluded), offsets the targets' row pointers, candidates |C_u| per row."""
+    ranks, candidates = np.asarray(ranks, dtype=np.int64), np.asarray(candidates, dtype=np.float64)
+    row = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
+    valid = ranks >= 0
+    out = {"skipped": int((~valid).sum()), "recall": {}, "ndcg": {}}
+    ranks, row = ranks[valid], row[valid]
+    if not len(ranks):
+        out.update(mpr=float("nan"), mrr=float("nan"), auc=float("nan"))
+        out["recall"], out["ndcg"] = {K: float("nan") for K in Ks}, {K: float("nan") for K in Ks}
+        return out
+    order = np.lexsort((ranks, row))  # every user's ranks ascending
+    ranks, row = ranks[order], row[order]
+    users, first, n_u = np.unique(row, return_index=True, return_counts=True)
+    cand = candidates[users]
+    out["mpr"] = float(np.mean(ranks / np.maximum(candidates[row] - 1.0, 1.0)))
+    out["mrr"] = float(np.mean(1.0 / (1.0 + ranks[first])))
+    # target number p of a user, in ascending order, has rank - p negatives above it
+    above = np.add.reduceat((ranks - (np.arange(len(ranks)) - np.repeat(first, n_u))).astype(np.float64), first)
+    negatives = cand - n_u
+    has = negatives > 0
+    out["auc"] = float(np.mean(1.0 - above[has] / (n_u[has] * negatives[has]))) if has.any() else float("nan")
+    for K in Ks:
+        cg = 1.0 / np.log2(np.arange(2, K + 2))  # the discount table of ranking_metrics_at_k
+        cg_sum = np.cumsum(cg)
+        hit = ranks < K
+        ideal = np.minimum(K, n_u)
+        out["recall"][K] = float(hit.sum() / ideal.sum())
+        dcg = np.add.reduceat(np.where(hit, cg[np.minimum(ranks, K - 1)], 0.0), first)
+        out["ndcg"][K] = float(np.mean(dcg / cg_sum[ideal - 1]))
+    return out
+
+
+def full_ranking_metrics(model, train_user_items, test_user_items, K=(10,), show_progress=True,
+                         batch_size=DEFAULT_BATCH_SIZE, return_ranks=False):
+    """Metrics over the WHOLE catalogue of a fitted matrix-factorisation model: every held-out item's rank among all the items
+    its user could be recommended (the items outside the user's train row; 0-based, exact score ties go to the lower id),
+    computed by KnnQuery.target_ranks without a score matrix.  Every stored index of test_user_items is a target (the
+    pattern only: values carry no weight); a target stored in the user's train row is no candidate and is left out.  Users
+    with nothing held out are not queried.  Returns a dict:
+      "mpr"     mean over the pairs of rank / max(candidates - 1, 1) -- the expected percentile rank of Hu, Koren and Volinsky
+                (2008), unweighted, in [0, 1], lower is better
+      "mrr"     mean over the users of 1 / (1 + best rank)
+      "auc"     mean over the users of the exact AUC, positives = the user's targets, negatives = the other candidates
+                (users without negatives are left out)
+      "recall", "ndcg"   dicts keyed by each K: a target is a hit when rank < K; denominators and the discount table are
+                those of ranking_metrics_at_k (sum of min(K, targets) over the users; the ideal DCG of min(K, targets) hits)
+      "skipped" the targets left out
+    return_ranks adds "ranks": {"users", "offsets", "targets", "ranks", "candidates"}, the queried users in ascending order
+    and the arrays of KnnQuery.target_ranks over them (rank -1: skipped).  K: an int or a sequence of ints >= 1.
+    NotImplementedError for a model whose scores are not dot products of factors.  Runs on the GPU only."""
+    import implicit_amd.gpu as gpu
+    from .ann.ivf import IVFModel
+    from .gpu.matrix_factorization_base import MatrixFactorizationBase
+
+    if isinstance(model, IVFModel):
+        model = model.model  # the exact model the index was built over
+    if not isinstance(model, MatrixFactorizationBase):
+        raise NotImplementedError(f"full_ranking_metrics ranks by dot products of user and item factors; the scores of "
+                                  f"{type(model).__name__} are not factor dot products")
+    if not gpu.HAS_CUDA:
+        raise ValueError("No usable HIP device / extension: implicit_amd.evaluation computes its metrics on the GPU")
+    if not isinstance(train_user_items, csr_matrix):
+        train_user_items = train_user_items.tocsr()
+    if not isinstance(test_user_items, csr_matrix):
+        test_user_items = test_user_items.tocsr()
+    Ks = tuple(int(k) for k in (K if np.iterable(K) else (K,)))
+    batch_size = int(batch_size)
+    if not Ks or min(Ks) < 1:
+        raise ValueError("every K must be >= 1")
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+
+    test = _canonical_pattern(test_user_items)
+    indptr = test.indptr.astype(np.int64)
+    users = np.flatnonzero(np.diff(indptr) > 0).astype(np.int32)
+    progress = _progress(len(users), show_progress)
+    ranks, candidates, targets, counts = [], [], [], []
+    for start in range(0, len(users), batch_size):
+        batch = users[start:start + batch_size]
+        rows = test[batch]
+        r, c = model.knn.target_ranks(model.item_factors, model._user_query(batch), rows.indptr, rows.indices,
+                                      query_filter=model._liked_filter(train_user_items[batch]))
+        ranks.append(r), candidates.append(c), targets.append(rows.indices.astype(np.int32)), counts.append(np.diff(rows.indptr))
+        progress.update(len(batch))
+    progress.close()
+    cat = lambda parts, dtype: np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)  # noqa: E731
+    ranks, candidates, targets = cat(ranks, np.int32), cat(candidates, np.int32), cat(targets, np.int32)
+    offsets = np.concatenate(([0], np.cumsum(cat(counts, np.int64)))).astype(np.int64)
+    out = _full_rank_sums(ranks, offsets, candidates, Ks)
+    if return_ranks:
+        out["ranks"] = {"users": users, "offsets": offsets, "targets": targets, "ranks": ranks, "candidates": candidates}
+    return out
+
+
+def mean_percentile_rank(model, train_user_items, test_user_items, show_progress=True, batch_size=DEFAULT_BATCH_SIZE):
+    """The mean percentile rank of the held-out items over the whole catalogue (full_ranking_metrics)."""
+    return full_ranking_metrics(model, train_user_items, test_user_items, (1,), show_progress, batch_size)["mpr"]
+
+
+def mean_reciprocal_rank(model, train_user_items, test_user_items, show_progress=True, batch_size=DEFAULT_BATCH_SIZE):
+    """The mean reciprocal rank of every user's best held-out item over the whole catalogue (full_ranking_metrics)."""
+    return full_ranking_metrics(model, train_user_items, test_user_items, (1,), show_progress, batch_size)["mrr"]
+
+
+def auc(model, train_user_items, test_user_items, show_progress=True, batch_size=DEFAULT_BATCH_SIZE):
+    """The exact AUC, held-out items against every other candidate, averaged over the users (full_ranking_metrics)."""
+    return full_ranking_metrics(model, train_user_items, test_user_items, (1,), show_progress, batch_size)["auc"]

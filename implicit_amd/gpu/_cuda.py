@@ -148,6 +148,28 @@ class KnnQuery:
                                       0 if rule == "dpp" else 1, float(param), float(min_gain), _vp(ids), _vp(gains), _vp(counts)))
         return ids, gains, counts
 
+    def target_ranks(self, items, m, offsets, targets, query_filter=None):
+        """NEW: where the targets of every query row stand among all the items that row could be recommended
+        (csrc/target_ranks.hip).  Row r of `m` owns the item ids targets[offsets[r]:offsets[r + 1]] (host arrays, int64 / int32,
+        strictly increasing inside a row); query_filter: the COOMatrix a top-k query takes, its entries are no candidates.
+        Returns (ranks, candidates): ranks int32, aligned with `targets` -- the number of candidates of the row that score
+        higher, or equally with a lower id; -1 for a target that is itself filtered -- and candidates int32, the candidates of
+        each row.  Scores are exact-fp32-product dot products, never stored.  A target id outside `items` raises IndexError."""
+        if not isinstance(items, Matrix) or not isinstance(m, Matrix):
+            raise TypeError("KnnQuery.target_ranks expects implicit.gpu.Matrix arguments")
+        if query_filter is not None and not isinstance(query_filter, COOMatrix):
+            raise TypeError("KnnQuery.target_ranks: query_filter must be an implicit_amd.gpu.COOMatrix")
+        rows = m.shape[0]
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        targets = np.ascontiguousarray(targets, dtype=np.int32)
+        if offsets.shape != (rows + 1,) or targets.ndim != 1 or len(targets) != (offsets[-1] if rows else 0):
+            raise ValueError("target_ranks: offsets must hold one entry per query row plus one and end at len(targets)")
+        ranks = np.empty(len(targets), dtype=np.int32)
+        candidates = np.empty(rows, dtype=np.int32)
+        check(lib().imp_knn_target_ranks(self._h, items._h, m._h, _vp(offsets), _vp(targets),
+                                         query_filter._h if query_filter is not None else None, _vp(ranks), _vp(candidates)))
+        return ranks, candidates
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib().imp_knn_destroy(self._h)

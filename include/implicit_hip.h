@@ -292,6 +292,21 @@ int imp_knn_rank(imp_knn *k, const imp_matrix *items, const imp_matrix *query, c
 int imp_knn_diversify(imp_knn *k, const imp_matrix *items, int64_t rows, const int64_t *offsets, const int32_t *candidates,
                       const float *quality, int n, int rule, float param, float min_gain, int32_t *indices, float *gains,
                       int32_t *counts);
+/* NEW: the rank of every target among all the items its query row could be recommended (csrc/target_ranks.hip).  items (n_items x
+ * C) and query (rows x C): fp32, 2 <= C <= 1024.  HOST inputs: offsets[rows + 1] and targets[offsets[rows]], row r holding the
+ * item ids targets[offsets[r] .. offsets[r + 1]), strictly increasing (a row may be empty).  query_filter: the device COO of a
+ * top-k query (row = query row, col = item), NULL or empty for none; C_r is every item without an entry in row r.  With
+ * s(r, j) the fp32 score -- exact fp32 products (v_mfma_f32_32x32x2_f32), summed in an order that depends on C alone, so one
+ * pair has one score wherever it is evaluated -- a target t in C_r gets
+ *   rank = #{ j in C_r, j != t : s(r, j) > s(r, t) or (s(r, j) == s(r, t) and j < t) }     (0-based; -0.0 as +0.0)
+ * and a target outside C_r gets -1.  The tie rule is this function's own: imp_knn_topk orders exact ties by descending id.
+ * HOST outputs: ranks[offsets[rows]], aligned with targets, and candidates[rows] = |C_r|.  Rows are processed in chunks whose
+ * exclusion bitmap fits half the handle's max_temp_memory; the chunking changes no result.  Counts are integers: bit-reproducible.
+ * No score is stored.  IMP_OUT_OF_RANGE for a target id outside [0, n_items), IMP_INVALID_ARGUMENT for column counts that differ
+ * or lie outside 2 .. 1024, a matrix that is not fp32, offsets that do not start at 0 or that decrease, targets of a row that
+ * are not strictly increasing -- all before anything is launched or written. */
+int imp_knn_target_ranks(imp_knn *k, const imp_matrix *items, const imp_matrix *query, const int64_t *offsets,
+                         const int32_t *targets, const imp_coo *query_filter, int32_t *ranks, int32_t *candidates);
 
 /* ---- RandomState (random.h:10-21, random.cu:14-40) ------------------------------------------- */
 int imp_random_create(int64_t seed, imp_random **out);
