@@ -11,7 +11,8 @@ has no Cholesky solver), the Comm class (RCCL exchange for the multi-GPU fit), l
 reference has no GPU LMF), SpMat / sparse_topk_product (the reference's nearest-neighbour models are CPU only), IVFIndex
 (a native IVF-Flat index in place of the faiss one the reference's ann wrappers build) and ease_gram / spd_inverse /
 ease_weights / ease_topk (the EASE model, which the reference does not have), slim_solve (the SLIM model, likewise), and
-spmm / multiply_small (the products of the randomized SVD behind PureSVD, which the reference does not have either).
+spmm / multiply_small (the products of the randomized SVD behind PureSVD, which the reference does not have either), and
+dae_encode / dae_gradients / dae_step (the Mult-DAE autoencoder, likewise).
 """
 import ctypes
 
@@ -579,6 +580,63 @@ def softmax_epoch(userids, itemids, indptr, X, Y, learning_rate, regularization,
                                    int(seed), negatives, -1 if samples is None else int(samples),
                                    ctypes.byref(correct), ctypes.byref(masked)))
     return correct.value, masked.value
+
+
+def _dae_rows(what, csr, rows, batch=False):
+    if not isinstance(csr, CSRMatrix):
+        raise TypeError(f"{what}: user_items must be an implicit_amd.gpu.CSRMatrix")
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    if rows.ndim != 1:
+        raise ValueError(f"{what}: rows must be a 1-d array of row ids")
+    if batch and (len(rows) < 64 or len(rows) % 64):
+        raise ValueError(f"{what}: batch_size must be a multiple of 64")
+    return rows
+
+
+def _dae_hidden(what, W_in):
+    hidden = W_in.shape[1]
+    if not 32 <= hidden <= 512 or hidden % 32:
+        raise ValueError(f"{what}: hidden must be a multiple of 32 in 32 .. 512")
+    return hidden
+
+
+def dae_encode(user_items, rows, W_in, b_in):
+    """NEW: the hidden rows of a Mult-DAE for serving (imp_dae_encode, mult_dae.hip): a Matrix [len(rows) x (hidden + 1)] with
+    h = tanh(b_in + sum_i W_in[i] / sqrt(n_u)) over each listed CSR row's items (no dropout) and 1.0 in the last column, the
+    query layout of KnnQuery against W_out.  rows: int ids into the CSRMatrix user_items, -1 for an empty row."""
+    rows = _dae_rows("dae_encode", user_items, rows)
+    out = Matrix.zeros(len(rows), _dae_hidden("dae_encode", W_in) + 1)
+    check(lib().imp_dae_encode(user_items._h, _vp(rows), len(rows), W_in._h, b_in._h, out._h))
+    return out
+
+
+def dae_gradients(user_items, rows, W_in, b_in, W_out, dropout=0.0, seed=0):
+    """NEW: loss and gradients of one Mult-DAE batch, nothing updated (imp_dae_gradients; mult_dae.hip states the model).
+    rows: the batch's row ids, a multiple of 64 of them, -1 for an empty row.  Returns (loss, dW_in, db_in, dW_out, dh, dz) as
+    a float and five new Matrix objects; the multinomial gradient g itself (batch x items) is never stored.  The dropout
+    mask is the Philox stream of (seed, CSR position)."""
+    rows = _dae_rows("dae_gradients", user_items, rows, batch=True)
+    hidden = _dae_hidden("dae_gradients", W_in)
+    outs = [Matrix.zeros(*W_in.shape), Matrix.zeros(1, hidden), Matrix.zeros(*W_out.shape), Matrix.zeros(len(rows), hidden),
+            Matrix.zeros(len(rows), hidden)]
+    loss = ctypes.c_float(0)
+    check(lib().imp_dae_gradients(user_items._h, _vp(rows), len(rows), W_in._h, b_in._h, W_out._h, float(dropout), int(seed),
+                                  *[m._h for m in outs], ctypes.byref(loss)))
+    return (loss.value, *outs)
+
+
+def dae_step(user_items, rows, params, moments, dropout, seed, learning_rate, step, regularization=0.0, beta1=0.9, beta2=0.999,
+             eps=1e-8):
+    """NEW: one Adam step of a Mult-DAE on one batch (imp_dae_step), returns the loss before the update.  params = (W_in, b_in,
+    W_out), moments = (m_W_in, v_W_in, m_b_in, v_b_in, m_W_out, v_W_out), all float32 Matrix objects updated in place; step
+    counts from 1 (the bias correction).  regularization is added to the gradients of W_in and W_out[:, :hidden] only."""
+    rows = _dae_rows("dae_step", user_items, rows, batch=True)
+    _dae_hidden("dae_step", params[0])
+    loss = ctypes.c_float(0)
+    check(lib().imp_dae_step(user_items._h, _vp(rows), len(rows), *[m._h for m in params], *[m._h for m in moments],
+                             float(dropout), int(seed), float(learning_rate), float(beta1), float(beta2), float(eps),
+                             float(regularization), int(step), ctypes.byref(loss)))
+    return loss.value
 
 
 def lmf_update(cui, X, Y, deriv_sum_sq, learning_rate, regularization, neg_prop, seed, one_col=-1):

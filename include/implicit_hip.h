@@ -387,6 +387,40 @@ int imp_softmax_update(const imp_intvector *userids, const imp_intvector *itemid
                        imp_matrix *Y, float learning_rate, float regularization, int64_t seed, int negatives, int64_t samples,
                        int64_t *correct, int64_t *masked);
 
+/* ---- NEW: Mult-DAE, the multinomial denoising autoencoder of Liang et al. (WWW 2018) with one hidden layer (no reference
+ * counterpart; csrc/mult_dae.hip states the contract in full).  Parameters, all fp32: W_in [items x H], b_in
+ * [1 x H], W_out [items x (H + 1)] with the output bias as its last column; H a multiple of 32 in 32 .. 512.  user_items: a CSR
+ * pattern (values ignored) with cols = items, in one block, every row strictly ascending.  rows: HOST array of row ids, -1 for
+ * an empty row.  Forward, row u with n_u entries at the CSR positions pos: weight m_pos s_u, s_u = 1 / ((1 - p) sqrt(n_u)),
+ * m_pos = 1 for dropout p = 0 and otherwise 1 when float(word 0 of Philox4x32-10(counter (pos, 0, 0, 7), key = seed) >> 8) *
+ * 2^-24 >= p;  z_u = b_in + sum of the weighted rows of W_in in stored order;  h_u = tanh(z_u);  logit_uj = W_out[j, :H] . h_u +
+ * W_out[j, H];  loss = (1 / B) sum_u (n_u lse_u - sum_{i in row u} logit_ui).  A row with n_u = 0 contributes nothing.
+ * Backward: g_uj = (n_u exp(logit_uj - lse_u) - x_uj) / B;  dW_out[j, :H] = sum_u g_uj h_u;  dW_out[j, H] = sum_u g_uj;
+ * dh_u = sum_j g_uj W_out[j, :H];  dz = dh (1 - h^2);  db_in = sum_u dz_u;  dW_in[i] = sum_u m_ui s_u dz_u.  The B x items logits
+ * are never stored: two passes over item tiles of 64 on the matrix cores (exact fp32 products in ascending k), a running
+ * (max, sum exp) per row.  loss, dW_out, dh, dz, db_in are bit-reproducible on one device; dW_in is summed with fp32 atomic
+ * adds and is not where three or more rows of the batch share an item.  All three calls are synchronous.
+ * IMP_INVALID_ARGUMENT, nothing written: a shape or dtype that disagrees with the above, H or batch_size out of range, dropout
+ * outside [0, 1), matrices sharing storage, a CSR in several blocks.  IMP_OUT_OF_RANGE: a row id outside [-1, rows).  A row
+ * that is not strictly ascending is found on the device: IMP_INVALID_ARGUMENT, gradients undefined, parameters untouched. */
+/* out [n_rows x (H + 1)]: h of the listed rows without dropout, 1.0 in the last column -- the query rows of the serving
+ * kernels against W_out.  Any n_rows >= 0. */
+int imp_dae_encode(const imp_csr *user_items, const int32_t *rows, int64_t n_rows, const imp_matrix *W_in, const imp_matrix *b_in,
+                   imp_matrix *out);
+/* The loss and the five gradient arrays of one batch (batch_size a multiple of 64): dW_in, db_in, dW_out shaped like their
+ * parameters, dh and dz [batch_size x H].  Updates nothing. */
+int imp_dae_gradients(const imp_csr *user_items, const int32_t *rows, int64_t batch_size, const imp_matrix *W_in,
+                      const imp_matrix *b_in, const imp_matrix *W_out, float dropout, int64_t seed, imp_matrix *dW_in,
+                      imp_matrix *db_in, imp_matrix *dW_out, imp_matrix *dh, imp_matrix *dz, float *loss);
+/* The gradients of the batch, then one dense Adam step on every parameter: grad = gradient + regularization * parameter for
+ * W_in and W_out[:, :H] (not the biases); m = beta1 m + (1 - beta1) grad; v = beta2 v + (1 - beta2) grad^2; parameter -=
+ * learning_rate (m c1) / (sqrt(v c2) + eps), c1 = 1 / (1 - beta1^step), c2 = 1 / (1 - beta2^step), step >= 1.  The moment
+ * matrices are shaped like their parameters.  Returns the loss before the update. */
+int imp_dae_step(const imp_csr *user_items, const int32_t *rows, int64_t batch_size, imp_matrix *W_in, imp_matrix *b_in,
+                 imp_matrix *W_out, imp_matrix *m_W_in, imp_matrix *v_W_in, imp_matrix *m_b_in, imp_matrix *v_b_in,
+                 imp_matrix *m_W_out, imp_matrix *v_W_out, float dropout, int64_t seed, float learning_rate, float beta1,
+                 float beta2, float eps, float regularization, int64_t step, float *loss);
+
 /* ---- LMF training (no reference GPU counterpart: implicit/lmf.py raises for use_gpu=True) --------------------------- */
 /* One Adagrad half-sweep of Logistic Matrix Factorization: X (rows of cui x C) is updated against the read-only Y (columns
  * of cui x C), deriv_sum_sq (shape of X) accumulates the squared gradients.  fp32, C = factors + 2 in 3 .. 1024.  The
