@@ -15,7 +15,7 @@ OBJDIR = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libimplicit_hip.so")
 SOURCES = ["containers.hip", "csr_schedule.hip", "als_cg.hip", "als_cg_q.hip", "als_cg_qf.hip", "als_cg_qh.hip", "als_cg_fixup.hip", "als_cg_nm.hip", "als_cg_w256.hip", "als_pad.hip", "als_cholesky.hip", "als_subspace.hip", "gramian.hip", "solver.hip", "topk.hip",
            "random.hip", "comm.hip", "pair_sgd.hip", "bpr.hip", "warp.hip", "hybrid_warp.hip", "lmf.hip", "knn.hip", "evaluation.hip", "ivf.hip", "explain.hip", "rank.hip",
-           "ease.hip", "spd_inverse.hip", "svd.hip", "slim.hip", "softmax_mf.hip", "diversify.hip", "target_ranks.hip", "mult_dae.hip"]
+           "ease.hip", "spd_inverse.hip", "svd.hip", "slim.hip", "softmax_mf.hip", "diversify.hip", "target_ranks.hip", "mult_dae.hip", "mult_vae.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-pass-failed", "-ffp-contract=off"]
@@ -25,12 +25,14 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # diversify.hip, target_ranks.hip: the same
 # softmax_mf.hip: the same, and -munsafe-fp-atomics so that its fp32 adds are global_atomic_add_f32, not compare-and-swap loops
 # mult_dae.hip: -munsafe-fp-atomics for the same reason (the scatter of dW_in)
+# mult_vae.hip: the same scatter, through mult_dae_kernels.h
 EXTRA_FLAGS = {"als_cholesky.hip": ["-fno-slp-vectorize"],
                "hybrid_warp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "diversify.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "softmax_mf.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-munsafe-fp-atomics"],
                "target_ranks.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-               "mult_dae.hip": ["-munsafe-fp-atomics"]}
+               "mult_dae.hip": ["-munsafe-fp-atomics"],
+               "mult_vae.hip": ["-munsafe-fp-atomics"]}
 
 
 def _deps():

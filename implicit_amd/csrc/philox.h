@@ -4,6 +4,7 @@
 //   0  RandomState::uniform    1  RandomState::randn    2  bpr_update sample pairs    3  lmf_update negatives
 //   4  warp_update positives and candidates    5  hybrid_warp_update positives and candidates
 //   6  softmax_update positives and shared negatives    7  dae_gradients / dae_step dropout masks
+//   8  vae_gradients / vae_step reparameterisation draws (counter (batch slot, code column, 0, 8))
 #ifndef IMPLICIT_AMD_CSRC_PHILOX_H_
 #define IMPLICIT_AMD_CSRC_PHILOX_H_
 #include <hip/hip_runtime.h>

@@ -12,7 +12,8 @@ reference has no GPU LMF), SpMat / sparse_topk_product (the reference's nearest-
 (a native IVF-Flat index in place of the faiss one the reference's ann wrappers build) and ease_gram / spd_inverse /
 ease_weights / ease_topk (the EASE model, which the reference does not have), slim_solve (the SLIM model, likewise), and
 spmm / multiply_small (the products of the randomized SVD behind PureSVD, which the reference does not have either), and
-dae_encode / dae_gradients / dae_step (the Mult-DAE autoencoder, likewise).
+dae_encode / dae_gradients / dae_step and vae_encode / vae_gradients / vae_step (the Mult-DAE and Mult-VAE autoencoders,
+likewise).
 """
 import ctypes
 
@@ -637,6 +638,57 @@ def dae_step(user_items, rows, params, moments, dropout, seed, learning_rate, st
                              float(dropout), int(seed), float(learning_rate), float(beta1), float(beta2), float(eps),
                              float(regularization), int(step), ctypes.byref(loss)))
     return loss.value
+
+
+def _vae_latent(what, W_dec):
+    latent = W_dec.shape[0]
+    if not 32 <= latent <= 256 or latent % 32:
+        raise ValueError(f"{what}: latent must be a multiple of 32 in 32 .. 256")
+    return latent
+
+
+def vae_encode(user_items, rows, params):
+    """NEW: the decoder-side hidden rows of a Mult-VAE for serving (imp_vae_encode, mult_vae.hip): a Matrix [len(rows) x
+    (hidden + 1)] holding [h2 | 1] with z = mu and no dropout, the query layout of KnnQuery against W_out.  params: (W_in, b_in,
+    W_lat, b_lat, W_dec, b_dec) or all seven; rows: int ids into the CSRMatrix user_items, -1 for an empty row."""
+    rows = _dae_rows("vae_encode", user_items, rows)
+    out = Matrix.zeros(len(rows), _dae_hidden("vae_encode", params[0]) + 1)
+    _vae_latent("vae_encode", params[4])
+    check(lib().imp_vae_encode(user_items._h, _vp(rows), len(rows), *[m._h for m in params[:6]], out._h))
+    return out
+
+
+def vae_gradients(user_items, rows, params, dropout=0.0, seed=0, beta=0.0, sample=True):
+    """NEW: one Mult-VAE batch, nothing updated (imp_vae_gradients; mult_vae.hip states the model).  params = (W_in, b_in, W_lat,
+    b_lat, W_dec, b_dec, W_out); rows: the batch's row ids, a multiple of 64 of them, -1 for an empty row.  Returns a dict: nll
+    and kl (floats; the loss is nll + beta kl), the seven gradients dW_in .. dW_out shaped like their parameters, and the stages
+    mu_lv [B x 2 latent], eps [B x latent] (the Philox draws of (seed, slot, column); zeros when sample is false) and dh2."""
+    rows = _dae_rows("vae_gradients", user_items, rows, batch=True)
+    hidden, latent = _dae_hidden("vae_gradients", params[0]), _vae_latent("vae_gradients", params[4])
+    names = ("dW_in", "db_in", "dW_lat", "db_lat", "dW_dec", "db_dec", "dW_out", "mu_lv", "eps", "dh2")
+    outs = [Matrix.zeros(*p.shape) for p in params]
+    outs += [Matrix.zeros(len(rows), 2 * latent), Matrix.zeros(len(rows), latent), Matrix.zeros(len(rows), hidden)]
+    nll, kl = ctypes.c_float(0), ctypes.c_float(0)
+    check(lib().imp_vae_gradients(user_items._h, _vp(rows), len(rows), *[m._h for m in params], float(dropout), int(seed),
+                                  float(beta), int(bool(sample)), *[m._h for m in outs], ctypes.byref(nll), ctypes.byref(kl)))
+    return dict(zip(names, outs), nll=nll.value, kl=kl.value)
+
+
+def vae_step(user_items, rows, params, moments, dropout, seed, beta, learning_rate, step, regularization=0.0, beta1=0.9,
+             beta2=0.999, eps=1e-8):
+    """NEW: one Adam step of a Mult-VAE on one batch (imp_vae_step), returns (nll, kl) before the update.  params as for
+    vae_gradients, moments = (m, v) per parameter in that order, fourteen float32 Matrix objects; all updated in place.  step
+    counts from 1.  regularization is added to the gradients of the four weight matrices only."""
+    rows = _dae_rows("vae_step", user_items, rows, batch=True)
+    _dae_hidden("vae_step", params[0]), _vae_latent("vae_step", params[4])
+    if len(params) != 7 or len(moments) != 14:
+        raise ValueError("vae_step: seven parameters and fourteen moment matrices")
+    nll, kl = ctypes.c_float(0), ctypes.c_float(0)
+    check(lib().imp_vae_step(user_items._h, _vp(rows), len(rows), (ctypes.c_void_p * 7)(*[m._h for m in params]),
+                             (ctypes.c_void_p * 14)(*[m._h for m in moments]), float(dropout), int(seed), float(beta),
+                             float(learning_rate), float(beta1), float(beta2), float(eps), float(regularization), int(step),
+                             ctypes.byref(nll), ctypes.byref(kl)))
+    return nll.value, kl.value
 
 
 def lmf_update(cui, X, Y, deriv_sum_sq, learning_rate, regularization, neg_prop, seed, one_col=-1):

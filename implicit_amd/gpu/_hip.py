@@ -122,6 +122,13 @@ _SIGNATURES = {
     "imp_dae_step": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 9 +
                     [ctypes.c_float, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                      ctypes.c_int64, ctypes.POINTER(ctypes.c_float)],
+    "imp_vae_encode": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 7,
+    "imp_vae_gradients": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 7 +
+                         [ctypes.c_float, ctypes.c_int64, ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 10 +
+                         [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
+    "imp_vae_step": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                     ctypes.c_float, ctypes.c_int64] + [ctypes.c_float] * 6 +
+                    [ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
     "imp_lmf_update": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
                        ctypes.c_int, ctypes.c_int64, ctypes.c_int],
     "imp_spmat_create": [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -421,6 +421,45 @@ int imp_dae_step(const imp_csr *user_items, const int32_t *rows, int64_t batch_s
                  imp_matrix *m_W_out, imp_matrix *v_W_out, float dropout, int64_t seed, float learning_rate, float beta1,
                  float beta2, float eps, float regularization, int64_t step, float *loss);
 
+/* ---- NEW: Mult-VAE, the variational autoencoder of the same paper (Mult-VAE^PR) with one tanh layer on either side of a
+ * Gaussian code (no reference counterpart; csrc/mult_vae.hip states the contract in full).  Parameters, all fp32,
+ * always in this order: W_in [items x H], b_in [1 x H], W_lat [H x 2L] and b_lat [1 x 2L] (columns 0 .. L - 1: mu, L .. 2L - 1:
+ * the log-variance lv), W_dec [L x H], b_dec [1 x H], W_out [items x (H + 1)] with the output bias last.  H a multiple of 32 in
+ * 32 .. 512, L a multiple of 32 in 32 .. 256.  user_items and rows as for Mult-DAE.  Forward, batch slot r: h1 = the Mult-DAE
+ * encoder's h;  [mu | lv] = b_lat + h1 W_lat;  eps = 0 when sample = 0, otherwise R = Philox4x32-10(counter (r, l, 0, 8), key =
+ * seed), u1 = (float(R.x >> 8) + 0.5f) 2^-24, u2 = float(R.y >> 8) 2^-24, eps = sqrtf(-2 logf(u1)) cosf(2 pi u2);  z = mu + eps
+ * exp(0.5 lv);  h2 = tanh(b_dec + z W_dec);  logits, lse and the multinomial NLL from h2 as Mult-DAE's from h;  KL = (1 / B)
+ * sum over the non-empty rows of sum_l 0.5 (exp(lv) + mu^2 - 1 - lv);  loss = NLL + beta KL.  Backward: dz2 = dh2 (1 - h2^2);
+ * db_dec = sum_r dz2;  dW_dec = z^T dz2;  dzl = dz2 W_dec^T;  dmu = dzl + (beta / B) mu;  dlv = 0.5 dzl eps exp(0.5 lv) +
+ * (beta / 2B)(exp(lv) - 1), both 0 for an empty row;  da = [dmu | dlv];  db_lat = sum_r da;  dW_lat = h1^T da;  dh1 = da W_lat^T;
+ * dz1 = dh1 (1 - h1^2);  db_in = sum_r dz1;  dW_in = the Mult-DAE scatter of dz1.  Every dense product is exact fp32 on the
+ * matrix cores, one chain per element in ascending inner index; everything but dW_in is bit-reproducible on one device.
+ * All three calls are synchronous.  IMP_INVALID_ARGUMENT, nothing written: a shape or dtype that disagrees with the above, H,
+ * L or batch_size out of range, dropout outside [0, 1), beta < 0, matrices sharing storage, a CSR in several blocks.
+ * IMP_OUT_OF_RANGE: a row id outside [-1, rows).  A row that is not strictly ascending is found on the device:
+ * IMP_INVALID_ARGUMENT, gradients undefined, parameters untouched. */
+/* out [n_rows x (H + 1)]: [h2 | 1] of the listed rows with z = mu and no dropout -- the query rows of the serving kernels
+ * against W_out.  Any n_rows >= 0. */
+int imp_vae_encode(const imp_csr *user_items, const int32_t *rows, int64_t n_rows, const imp_matrix *W_in, const imp_matrix *b_in,
+                   const imp_matrix *W_lat, const imp_matrix *b_lat, const imp_matrix *W_dec, const imp_matrix *b_dec,
+                   imp_matrix *out);
+/* NLL, KL and the seven gradients of one batch (batch_size a multiple of 64), each shaped like its parameter, and three
+ * intermediate stages: mu_lv [batch_size x 2L], eps [batch_size x L] (the draws; 0 when sample = 0), dh2 [batch_size x H].
+ * Updates nothing. */
+int imp_vae_gradients(const imp_csr *user_items, const int32_t *rows, int64_t batch_size, const imp_matrix *W_in,
+                      const imp_matrix *b_in, const imp_matrix *W_lat, const imp_matrix *b_lat, const imp_matrix *W_dec,
+                      const imp_matrix *b_dec, const imp_matrix *W_out, float dropout, int64_t seed, float beta, int sample,
+                      imp_matrix *dW_in, imp_matrix *db_in, imp_matrix *dW_lat, imp_matrix *db_lat, imp_matrix *dW_dec,
+                      imp_matrix *db_dec, imp_matrix *dW_out, imp_matrix *mu_lv, imp_matrix *eps, imp_matrix *dh2, float *nll,
+                      float *kl);
+/* The gradients of the batch with sample = 1, then Mult-DAE's dense Adam rule on every parameter; regularization is added to
+ * the gradients of W_in, W_lat, W_dec and W_out[:, :H] only.  params: the seven parameters in the order above; moments: the
+ * fourteen moment matrices (m, v) per parameter in that order, each shaped like its parameter.  Returns NLL and KL before the
+ * update. */
+int imp_vae_step(const imp_csr *user_items, const int32_t *rows, int64_t batch_size, imp_matrix *const *params,
+                 imp_matrix *const *moments, float dropout, int64_t seed, float beta, float learning_rate, float beta1,
+                 float beta2, float eps, float regularization, int64_t step, float *nll, float *kl);
+
 /* ---- LMF training (no reference GPU counterpart: implicit/lmf.py raises for use_gpu=True) --------------------------- */
 /* One Adagrad half-sweep of Logistic Matrix Factorization: X (rows of cui x C) is updated against the read-only Y (columns
  * of cui x C), deriv_sum_sq (shape of X) accumulates the squared gradients.  fp32, C = factors + 2 in 3 .. 1024.  The
