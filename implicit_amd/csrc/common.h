@@ -250,6 +250,7 @@ struct Context {
   size_t slim_items = 0;                         // order of the last imp_slim_solve: where the counts sit in slim_ws
   DeviceArray<float> div_basis;                  // Gram-Schmidt bases of a chunk of lists where they outgrow the LDS (diversify.hip)
   DeviceArray<float> dae_ws;                     // temporaries of a Mult-DAE batch and the gradients of imp_dae_step (mult_dae.hip)
+  DeviceArray<float> gru_ws;                     // id words, plans, temporaries and gradients of the GRU4Rec calls (gru4rec.hip)
 };
 inline hipStream_t stream() { return ctx().stream; }
 

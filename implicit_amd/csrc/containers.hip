@@ -500,6 +500,7 @@ int imp_release_workspaces(void) {
     c.slim_items = 0;
     c.div_basis = {};
     c.dae_ws = {};
+    c.gru_ws = {};
     std::lock_guard<std::mutex> g(c.small_mutex);
     for (auto &list : c.small_free) {
       for (void *p : list) (void)hipFree(p);

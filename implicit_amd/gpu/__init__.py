@@ -12,7 +12,7 @@ HAS_RMM = False
 try:
     from ._cuda import (COOMatrix, Comm, CSRMatrix, IntVector, IVFIndex, KnnQuery, LeastSquaresSolver, Matrix,  # noqa: F401
                         Profiler, RandomState, RankingMetrics, SpMat, bpr_epoch, bpr_update, calculate_norms, core_clock_mhz, debug_occupy, fixup_rows, get_device, get_device_count, get_oversubscribe, host_ranking_metrics, lmf_update, release_workspaces,
-                        set_deferred_sync, set_device, set_oversubscribe, sparse_topk_product, synchronize, warp_epoch, hybrid_warp_epoch, softmax_epoch, dae_encode, dae_gradients, dae_step, vae_encode, vae_gradients, vae_step,
+                        set_deferred_sync, set_device, set_oversubscribe, sparse_topk_product, synchronize, warp_epoch, hybrid_warp_epoch, softmax_epoch, dae_encode, dae_gradients, dae_step, vae_encode, vae_gradients, vae_step, gru_encode, gru_fold_plan, gru_gradients, gru_steps,
                         ease_gram, ease_topk, ease_weights, mem_get_info, multiply_small, slim_solve, slim_stats, slim_workspace_bytes, SLIM_MAX_ITEMS,
                         spd_inverse, spmm)
     from ._rsvd import randomized_svd  # noqa: F401

@@ -691,6 +691,73 @@ def vae_step(user_items, rows, params, moments, dropout, seed, beta, learning_ra
     return nll.value, kl.value
 
 
+def _gru_ids(what, a, ndim):
+    a = np.asarray(a)
+    if a.ndim != ndim or not (np.issubdtype(a.dtype, np.integer) or a.dtype == bool or a.size == 0):
+        raise ValueError(f"{what}: the id arrays must be {ndim}-d integer arrays")
+    if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+        raise IndexError(f"{what}: an id beyond int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def gru_gradients(params, h, inputs, targets, reset, negatives, loss="bpr-max", bpreg=1.0):
+    """NEW: one GRU4Rec step, nothing updated (imp_gru_gradients; gru4rec.hip states the model).  params = (W_x, W_h, b, W_out),
+    h the slots' state [B x hidden]; inputs, targets, reset: host int arrays [B] (-1 input: an idle slot), negatives [N].
+    Returns a dict: loss (float) and the new Matrix objects h1, da [B x 3 hidden] and dcol [(B + N) x (hidden + 1)] (per slot and
+    per column, before the fold), dh1, dW_h, db."""
+    inputs, targets, reset, negatives = (_gru_ids("gru_gradients", a, 1) for a in (inputs, targets, reset, negatives))
+    B, N, H = len(inputs), len(negatives), params[1].shape[0]
+    if len(targets) != B or len(reset) != B:
+        raise ValueError("gru_gradients: inputs, targets and reset must have one entry per slot")
+    names = ("h1", "da", "dcol", "dh1", "dW_h", "db")
+    outs = [Matrix.zeros(B, H), Matrix.zeros(B, 3 * H), Matrix.zeros(B + N, H + 1), Matrix.zeros(B, H), Matrix.zeros(H, 3 * H),
+            Matrix.zeros(1, 3 * H)]
+    value = ctypes.c_float(0)
+    check(lib().imp_gru_gradients(*[m._h for m in params], h._h, _vp(inputs), _vp(targets), _vp(reset), B, _vp(negatives), N,
+                                  str(loss).encode(), float(bpreg), *[m._h for m in outs], ctypes.byref(value)))
+    return dict(zip(names, outs), loss=value.value)
+
+
+def gru_steps(params, accumulators, h, inputs, targets, reset, negatives, loss="bpr-max", bpreg=1.0, learning_rate=0.1):
+    """NEW: T consecutive GRU4Rec training steps in one call (imp_gru_steps): the gradients of each step, then one Adagrad
+    update in which a row that occurs several times receives the sum of its occurrences once.  params = (W_x, W_h, b, W_out),
+    accumulators shaped like them, h [B x hidden]: all updated in place.  inputs, targets, reset: host int arrays [T x B],
+    negatives [T x N].  Returns the T losses (float32 array), each taken before its step's update."""
+    inputs, targets, reset, negatives = (_gru_ids("gru_steps", a, 2) for a in (inputs, targets, reset, negatives))
+    T, B = inputs.shape
+    if targets.shape != (T, B) or reset.shape != (T, B) or negatives.shape[0] != T:
+        raise ValueError("gru_steps: inputs, targets, reset must be [steps x batch_size] and negatives [steps x n]")
+    if len(params) != 4 or len(accumulators) != 4:
+        raise ValueError("gru_steps: four parameters and four accumulators")
+    losses = np.zeros(T, dtype=np.float32)
+    check(lib().imp_gru_steps((ctypes.c_void_p * 4)(*[m._h for m in params]), (ctypes.c_void_p * 4)(*[m._h for m in accumulators]),
+                              h._h, _vp(inputs), _vp(targets), _vp(reset), T, B, _vp(negatives), negatives.shape[1],
+                              str(loss).encode(), float(bpreg), float(learning_rate), _vp(losses)))
+    return losses
+
+
+def gru_encode(offsets, items, W_x, W_h, b):
+    """NEW: [h | 1] after the last item of each session (imp_gru_encode), a Matrix [sessions x (hidden + 1)] in the query layout
+    of KnnQuery against W_out.  Session s is items[offsets[s]:offsets[s + 1]]; an empty session gives h = 0."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    items = _gru_ids("gru_encode", items, 1)
+    if offsets.ndim != 1 or len(offsets) < 1 or offsets[-1] != len(items):
+        raise ValueError("gru_encode: offsets must hold sessions + 1 entries and end at len(items)")
+    out = Matrix.zeros(len(offsets) - 1, W_h.shape[0] + 1)
+    check(lib().imp_gru_encode(W_x._h, W_h._h, b._h, _vp(offsets), _vp(items), len(offsets) - 1, out._h))
+    return out
+
+
+def gru_fold_plan(ids):
+    """NEW: the host-side fold plan of a step's ids (imp_host_gru_fold_plan; needs no device): (unique, start, occ) -- the ids
+    >= 0 that occur, ascending, and occ[start[u]:start[u + 1]] the ascending positions at which unique[u] occurs."""
+    ids = _gru_ids("gru_fold_plan", ids, 1)
+    unique, start, occ = np.zeros(len(ids), np.int32), np.zeros(len(ids) + 1, np.int32), np.zeros(len(ids), np.int32)
+    n_unique, n_occ = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().imp_host_gru_fold_plan(_vp(ids), len(ids), _vp(unique), _vp(start), _vp(occ), ctypes.byref(n_unique), ctypes.byref(n_occ)))
+    return unique[:n_unique.value], start[:n_unique.value + 1], occ[:n_occ.value]
+
+
 def lmf_update(cui, X, Y, deriv_sum_sq, learning_rate, regularization, neg_prop, seed, one_col=-1):
     """One Adagrad half-sweep of Logistic Matrix Factorization (imp_lmf_update, lmf.hip): X is updated in place against
     the read-only Y over the CSRMatrix `cui` (rows of X x rows of Y, values = confidences), deriv_sum_sq (the shape of X)

@@ -129,6 +129,14 @@ _SIGNATURES = {
     "imp_vae_step": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                      ctypes.c_float, ctypes.c_int64] + [ctypes.c_float] * 6 +
                     [ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
+    "imp_gru_gradients": [ctypes.c_void_p] * 8 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_float] +
+                         [ctypes.c_void_p] * 6 + [ctypes.POINTER(ctypes.c_float)],
+    "imp_gru_steps": [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_void_p] * 4 +
+                     [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_float, ctypes.c_float,
+                      ctypes.c_void_p],
+    "imp_gru_encode": [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_void_p],
+    "imp_host_gru_fold_plan": [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
     "imp_lmf_update": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
                        ctypes.c_int, ctypes.c_int64, ctypes.c_int],
     "imp_spmat_create": [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -460,6 +460,53 @@ int imp_vae_step(const imp_csr *user_items, const int32_t *rows, int64_t batch_s
                  imp_matrix *const *moments, float dropout, int64_t seed, float beta, float learning_rate, float beta1,
                  float beta2, float eps, float regularization, int64_t step, float *nll, float *kl);
 
+/* ---- NEW: GRU4Rec, session-based next-item recommendation (Hidasi et al., ICLR 2016; Hidasi and Karatzoglou, CIKM 2018): one GRU
+ * layer on one-hot item input, trained session-parallel (no reference counterpart; csrc/gru4rec.hip states the contract in
+ * full).  Parameters, all fp32, always in this order: W_x [items x 3H] (columns 0 .. H - 1 the reset gate r, H ..
+ * 2H - 1 the update gate z, 2H .. 3H - 1 the candidate c), W_h [H x 3H], b [1 x 3H], W_out [items x (H + 1)] with the output bias
+ * last.  H a multiple of 32 in 32 .. 512.  A step works on B slots, B = batch_size a multiple of 64 in 64 .. 1024.  HOST arrays of a
+ * step: inputs[r] (an item, -1: idle slot), targets[r] (the item that follows), reset[r] (non-zero: the slot starts a session),
+ * negatives[n] for n < N = n_negatives, a multiple of 64 in 0 .. 4096.  Device state h [B x H].  Forward, active slot r with
+ * input i: h0 = 0 when reset[r], else h[r];  a_rz = W_x[i, :2H] + b[:2H] + h0 W_h[:, :2H];  r = sigmoid(a_r), z = sigmoid(a_z);
+ * c = tanh(W_x[i, 2H:] + b[2H:] + (r o h0) W_h[:, 2H:]);  h1 = (1 - z) o h0 + z o c.  An idle slot keeps its row of h and
+ * contributes nothing.  Scores s_rj = W_out[item_j, :H] . h1_r + W_out[item_j, H] over S = B + N columns: column j < B is
+ * targets[j] (an idle slot's column takes part in no row), column B + n is negatives[n]; column j != r is masked for row r when
+ * item_j = targets[r].  A = the number of active slots (A = 0: loss 0, no update).  loss "cross-entropy": (1 / A) sum_r (lse_r -
+ * s_rr), lse over the unmasked columns of row r, its own included.  loss "bpr-max": over the unmasked negatives j != r with
+ * p_rj their softmax, (1 / A) sum_r (-log(sum_j p_rj sigmoid(s_rr - s_rj) + 1e-24) + bpreg sum_j p_rj s_rj^2), a row without an
+ * unmasked negative contributing 0.  Backward, truncated at the step: g = dL/ds;  dcol_j = sum_r g_rj [h1_r | 1];  dh1_r = sum_j
+ * g_rj W_out[item_j, :H];  dz = dh1 o (c - h0) o z (1 - z);  dc = dh1 o z o (1 - c^2);  dr = (dc W_h[:, 2H:]^T) o h0 o r (1 - r);
+ * da = [dr | dz | dc];  db = sum_r da_r;  dW_h[:, :2H] = h0^T [dr | dz];  dW_h[:, 2H:] = (r o h0)^T dc;  dW_x[inputs[r]] += da_r.
+ * Every dense product is exact fp32 on the matrix cores, one chain per element in ascending inner index; everything returned
+ * or updated is bit-reproducible on one device.  IMP_INVALID_ARGUMENT, nothing written: a shape, dtype, H, batch_size,
+ * n_negatives or loss name outside the above, bpreg < 0, matrices sharing storage, an active slot with a negative target.
+ * IMP_OUT_OF_RANGE, nothing written: an input or target outside [-1, items), a negative or session item outside [0, items). */
+/* One step, nothing updated: the loss, h1 [B x H], da [B x 3H], dcol [S x (H + 1)], dh1 [B x H], dW_h [H x 3H], db [1 x 3H] -- da
+ * and dcol are per slot and per column, as the training path holds them before its fold. */
+int imp_gru_gradients(const imp_matrix *W_x, const imp_matrix *W_h, const imp_matrix *b, const imp_matrix *W_out,
+                      const imp_matrix *h, const int32_t *inputs, const int32_t *targets, const int32_t *reset, int64_t batch_size,
+                      const int32_t *negatives, int64_t n_negatives, const char *loss, float bpreg, imp_matrix *h1, imp_matrix *da,
+                      imp_matrix *dcol, imp_matrix *dh1, imp_matrix *dW_h, imp_matrix *db, float *loss_out);
+/* `steps` >= 1 consecutive steps: inputs, targets, reset [steps x B] and negatives [steps x N].  After each step's gradients
+ * one Adagrad update with one accumulator per parameter element, acc += G^2, p -= learning_rate G / sqrt(acc + 1e-6), G the
+ * step's whole gradient: an item row that occurs several times in a step (as an input, or among the S columns) receives ONE
+ * update from the SUM of its occurrences in ascending slot / column order; rows that do not occur are neither read nor written.
+ * h is carried from step to step and step t + 1 sees step t's update.  params and accumulators: four matrices each, in the
+ * order above, an accumulator shaped like its parameter.  Every step is queued without a host wait; losses[steps] (before
+ * each update) are read back once at the end. */
+int imp_gru_steps(imp_matrix *const *params, imp_matrix *const *accumulators, imp_matrix *h, const int32_t *inputs,
+                  const int32_t *targets, const int32_t *reset, int64_t steps, int64_t batch_size, const int32_t *negatives,
+                  int64_t n_negatives, const char *loss, float bpreg, float learning_rate, float *losses);
+/* out [n_sessions x (H + 1)] = [h after the session's last item | 1]: session s is items[offsets[s] .. offsets[s + 1]) (HOST
+ * arrays), forward only, many sessions advancing together; an empty session gives h = 0.  Any n_sessions >= 0. */
+int imp_gru_encode(const imp_matrix *W_x, const imp_matrix *W_h, const imp_matrix *b, const int64_t *offsets, const int32_t *items,
+                   int64_t n_sessions, imp_matrix *out);
+/* Host only: the fold plan of n ids (those < 0 take no part).  unique[*n_unique]: the ids that occur, ascending;  occ[*n_occ]:
+ * the positions of the ids >= 0, grouped by id, ascending within an id;  start[*n_unique + 1]: where each id's group begins.
+ * The three arrays must hold n, n + 1 and n entries. */
+int imp_host_gru_fold_plan(const int32_t *ids, int64_t n, int32_t *unique, int32_t *start, int32_t *occ, int64_t *n_unique,
+                           int64_t *n_occ);
+
 /* ---- LMF training (no reference GPU counterpart: implicit/lmf.py raises for use_gpu=True) --------------------------- */
 /* One Adagrad half-sweep of Logistic Matrix Factorization: X (rows of cui x C) is updated against the read-only Y (columns
  * of cui x C), deriv_sum_sq (shape of X) accumulates the squared gradients.  fp32, C = factors + 2 in 3 .. 1024.  The
